@@ -2,14 +2,28 @@
 """bench.py -- LZ4E scatter-gather block codec on MI355X (BASELINE.json metric).
 
 Metric: GiB/s compress+decompress (round trip, whole job), 64 KiB blocks,
-plus the ratio delta vs the reference: every frame of the run is compared
-with the CPU oracle's (tests-only restatement of the reference, used here as
-the checker) and the delta is computed from the two sets of sizes.
+plus (under ``--full``) the ratio delta vs the reference: every frame of the
+run is compared with the CPU oracle's (tests-only restatement of the
+reference, used here as the checker) and the delta is computed from the two
+sets of sizes.
 
 A step = one pass of the hot path over one batch of synthetic input already
 resident in HBM: LZ4E compress of every block (one launch), then LZ4E safe
 decompress of every frame (one launch).  value = uncompressed bytes of all
 ranks / max-over-ranks step time.
+
+A plain run (``--gpus 1 --steps N --warmup W``) does what ``value`` needs and
+no more: it builds the seeded corpus, warms up, times the N steps, checks the
+round trip on the device, writes ``--dump-outputs`` if asked, and prints the
+result line.  Everything else the benchmark measures or checks -- every frame
+against the CPU oracle, the CPU baselines, the strong-scaling line and the
+per-block floor, the end-to-end chunk-layer run, the single-call latencies,
+text256k's decompress-only leg -- runs under ``--full`` (the ``--no-*``
+options drop single legs of a full run).
+
+``--dump-outputs DIR`` writes what the last timed step left in the caller's
+buffers as ``DIR/<name>.npy`` (see :func:`dump_outputs`); the corpus is seeded,
+so two builds run with the same arguments can be compared array for array.
 
 Default workload (configs[1] of BASELINE.json): Silesia-proxy, 3234 blocks of
 64 KiB (~212 MB, the Silesia size) per GPU, each block a 16 x 4 KiB bio_vec
@@ -62,7 +76,7 @@ TOTAL_BYTES = {"text256k": 10**9}
 CORPUS_SEED = 0x5157
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -81,7 +95,17 @@ def parse():
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher check only: start the ranks (gloo), report, touch no GPU")
     ap.add_argument("--traffic-json", default=os.path.join(REPO, "profiles", "pmc_traffic.json"))
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline figure: oracle parity, CPU baselines, "
+                         "strong scaling and block floor, end to end, single calls, decompress-only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def _free_port() -> int:
@@ -201,6 +225,76 @@ class Batch:
             raise SystemExit("bench: round trip mismatch")
         self.rets = rets
         return int(rets.astype(np.int64).sum())
+
+
+DUMP_SEED = 0xD0C5
+DUMP_SAMPLE_BYTES = 4 << 20  # bytes of frames, and of decoded output, kept verbatim (as float32)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _row_checksums(rows, valid):
+    """Per row of a (n, width) uint8 tensor, over its first valid[i] bytes:
+    (sum of the bytes, sum of byte x (position % 65521 + 1)) -> float64 (n, 2),
+    exact (both stay far below 2^53).  Rows go through in slices so the int64
+    temporaries stay bounded."""
+    import torch
+    n, width = rows.shape
+    pos = torch.arange(width, dtype=torch.int64, device=rows.device)
+    wgt = pos % 65521 + 1
+    out = np.zeros((n, 2), np.float64)
+    step = max(1, (32 << 20) // max(1, width))
+    for a in range(0, n, step):
+        x = rows[a:a + step].to(torch.int64)
+        x = x * (pos[None, :] < valid[a:a + step, None].to(torch.int64))
+        out[a:a + step, 0] = x.sum(1).cpu().numpy()
+        out[a:a + step, 1] = (x * wgt[None, :]).sum(1).cpu().numpy()
+    return out
+
+
+def dump_outputs(b: Batch, out_dir: str, suffix: str = "") -> dict:
+    """What a caller of the timed path holds after its last step, as
+    out_dir/<name><suffix>.npy (float64 unless noted):
+
+    * compress_ret, decompress_ret -- every block's return value (frame size,
+      decoded size);
+    * frame_checksums, output_checksums -- (blocks, 2): two checksums of every
+      frame's bytes and of every decoded block's bytes (_row_checksums);
+    * sample_blocks -- the blocks kept verbatim: a fixed, seeded choice (all of
+      them when they fit in DUMP_SAMPLE_BYTES);
+    * frames_sample, output_sample -- float32 (sample, width): those blocks'
+      frame and decoded bytes, -1 past the returned size.
+
+    -> {name: bytes written}; at most DUMP_MAX_BYTES in all."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize(b.dev)
+    ret, dret = b.d_ret.clamp(min=0), b.d_dret.clamp(min=0)
+    frames = b.d_dst[:b.nblk * b.slot].view(b.nblk, b.slot)
+    decoded = b.d_out[:b.nblk * b.bs].view(b.nblk, b.bs)
+    k = max(1, min(b.nblk, DUMP_SAMPLE_BYTES // b.slot))
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(b.nblk, size=k, replace=False))
+    d_pick = torch.from_numpy(pick).to(b.dev)
+
+    def sample(rows, valid):
+        x = rows[d_pick].to(torch.float32)
+        past = torch.arange(rows.shape[1], device=b.dev)[None, :] >= valid[d_pick, None]
+        return x.masked_fill(past, -1.0).cpu().numpy()
+
+    arrays = {
+        "compress_ret": b.d_ret.cpu().numpy().astype(np.float64),
+        "decompress_ret": b.d_dret.cpu().numpy().astype(np.float64),
+        "frame_checksums": _row_checksums(frames, ret),
+        "output_checksums": _row_checksums(decoded, dret),
+        "sample_blocks": pick.astype(np.float64),
+        "frames_sample": sample(frames, ret),
+        "output_sample": sample(decoded, dret),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench: --dump-outputs would write {total} bytes (limit {DUMP_MAX_BYTES})")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+    return {name: a.nbytes for name, a in arrays.items()}
 
 
 def oracle_frames(host: np.ndarray, b: Batch, threads: int):
@@ -694,9 +788,14 @@ def main():
     U_all = U * world
     value = U_all / step_s / 2**30
 
+    # ---- the last timed step's outputs, before any other leg touches them ----
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(b, args.dump_outputs, f".rank{rank}" if world > 1 else "")
+
     # ---- every frame against the oracle (the ratio delta is measured) --------
     par = None
-    if not args.no_parity:
+    if args.full and not args.no_parity:
         par = parity(host, b, threads)
         if par["frames_identical"] != nblk:
             raise SystemExit(f"bench: {nblk - par['frames_identical']} frames differ from the oracle")
@@ -738,15 +837,18 @@ def main():
         "compress_GiBps": round(U_all / (comp_ms / 1e3) / 2**30, 3),
         "decompress_GiBps": round(U_all / (dec_ms / 1e3) / 2**30, 3),
         "roofline": roofline,
+        "full": args.full,
     }
+    if dumped is not None:
+        result["dump_outputs"] = {"dir": args.dump_outputs, "bytes": dumped}
 
     # ---- configs[4]: decompress-only (the HBM-roofline stress run) -------------
-    if args.workload == "text256k" and not args.no_decompress_only:
+    if args.full and args.workload == "text256k" and not args.no_decompress_only:
         result["decompress_only"] = decompress_only(b, args.steps, rank, world, dist, dev,
                                                     args.traffic_json, args.workload)
 
     # ---- strong scaling: one corpus over the N ranks (chunk queue) -------------
-    if not args.no_strong:
+    if args.full and not args.no_strong:
         # the step's per-block floor (after the timed region; rank 0's corpus
         # is the N=1 corpus): the strong line cannot exceed step(N=1) / floor
         floor = block_floor(b) if rank == 0 else None
@@ -762,15 +864,15 @@ def main():
             result["strong"]["ceiling_x"] = round(step_s * 1e3 / floor["floor_ms"], 3)
 
     # ---- end to end through the chunk layer (PCIe-inclusive, never `value`) ----
-    if world == 1 and not args.no_e2e:
+    if args.full and world == 1 and not args.no_e2e:
         result["end_to_end"] = end_to_end(host, lens, bs, seg)
 
     # ---- drop-in single calls (configs[0]) -------------------------------------
-    if world == 1 and not args.no_single_call:
+    if args.full and world == 1 and not args.no_single_call:
         result["single_call"] = single_call()
 
     # ---- CPU baseline (rank 0, N=1 only) ---------------------------------------
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import oracle_ref
         if par is None:
             _, _, tc, td = oracle_frames(host, b, threads)

@@ -201,6 +201,20 @@ def test_bench_launches_ranks():
     assert bad.returncode != 0 and "WORLD_SIZE" in bad.stderr
 
 
+def test_bench_options():
+    """bench.py's options: a plain run is not --full, --dump-outputs takes a
+    directory, and --steps must name at least one timed step."""
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, repo)
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, None)
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
 def test_rebalance_plan_moves_each_chunk_once():
     """3, 4 and 8 ranks, uneven busy times: no chunk appears twice in a plan
     (a chunk relayed through a middle rank would be forwarded, in the same
