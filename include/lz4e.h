@@ -375,6 +375,44 @@ struct lz4e_chunk_stats {
 int lz4e_chunk_write_batch(struct lz4e_chunk_request *reqs, int n,
 			   struct lz4e_chunk_stats *stats);
 
+/*
+ * Registered host memory: the zero-copy path of lz4e_chunk_write_batch.
+ * A block-device server that owns its I/O buffers (a ublk or SPDK-style
+ * buffer pool) registers them once.  A request whose memory is registered
+ * is then served without the pipeline's pinned staging and without a host
+ * memcpy on either side: the device gathers the source segments out of the
+ * caller's pages over PCIe and writes `data` and `frame` there itself; only
+ * descriptors go up and only metadata comes back.
+ *
+ * The path is chosen per request from its addresses, never on the caller's
+ * word: a request is zero-copy when every source byte its iterator covers,
+ * [data, data + bi_size) and, with `frame` set, [frame, frame + frame_cap)
+ * each lie wholly inside one live registration.  Any other request is staged
+ * as before, and one call may hold both kinds.  lz4e_chunk_write_batch's
+ * results -- status, comp_size, the bytes at `data` and `frame`, the stats --
+ * do not depend on registration; a failing request (-EIO, -ENOSPC) has
+ * nothing written to its `data` or `frame` on either path.
+ * LZ4E_CHUNK_ZERO_COPY=0 in the environment, read per call, stages every
+ * request.
+ *
+ * lz4e_register_host_memory pins [ptr, ptr + len) (hipHostRegister, mapped
+ * and portable) and records its device address.  Returns 0 on success; -22
+ * (-EINVAL) for a bad argument, without calling HIP: ptr NULL, len 0, ptr or
+ * len not a multiple of LZ4E_PAGE_SIZE, or a range that overlaps a live
+ * registration (adjacent ranges are fine; a buffer must lie inside ONE
+ * registration to count as registered); -1 when no gfx950 is usable or HIP
+ * refuses, with the reason in lz4e_last_error().
+ *
+ * lz4e_unregister_host_memory takes the base pointer of a live
+ * registration.  Returns 0; -2 (-ENOENT) when ptr is not such a base; -1 on
+ * a HIP failure (the range is forgotten all the same).  It takes the chunk
+ * pipeline's lock, so it waits for a lz4e_chunk_write_batch in flight and
+ * never pulls memory from under one.  The memory must stay allocated from
+ * register to unregister; unregister before freeing it.
+ */
+int lz4e_register_host_memory(void *ptr, size_t len);
+int lz4e_unregister_host_memory(void *ptr);
+
 #ifdef __cplusplus
 }
 #endif

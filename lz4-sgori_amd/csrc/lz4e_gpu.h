@@ -72,4 +72,44 @@ hipError_t launch_compress_stamped(const CompressBatch& a, hipStream_t stream, u
 hipError_t launch_decompress(const DecompressBatch& a, hipStream_t stream);
 hipError_t launch_decompress_stamped(const DecompressBatch& a, hipStream_t stream, uint64_t* dbg);
 
+// Zero-copy scatter-gather kernels (lz4e_sg.hip): the device reads and
+// writes registered host memory itself.  The descriptor formats say nothing
+// about the chunk pipeline, so the other host entry points can adopt them.
+//
+// Gather: `len` bytes at device-visible address `src` go to data + dst_off.
+// The host splits a segment into descriptors of at most kSgPiece bytes (one
+// workgroup each), so that a long segment is many PCIe reads in flight.
+constexpr uint32_t kSgPiece = 16384;
+struct SgGatherDesc {
+    uint64_t src;
+    uint64_t dst_off;
+    uint32_t len;
+    uint32_t reserved;
+};
+hipError_t launch_sg_gather(const SgGatherDesc* desc, uint32_t ndesc, uint8_t* data, hipStream_t stream);
+
+// Deliver: request `entry` of a round-trip batch.  When ret[entry] > 0,
+// dret[entry] == in_len[entry] and (frame == 0 or frame_cap >= ret[entry]),
+// ret[entry] bytes at data + fr_off[entry] go to `frame` (if set) and
+// in_len[entry] bytes at data + out_off[entry] to `data`; otherwise nothing
+// is written.
+struct SgDeliverDesc {
+    uint64_t frame;  // device-visible address, 0: no frame wanted
+    uint64_t data;   // device-visible address
+    uint32_t entry;
+    int32_t frame_cap;
+};
+struct SgDeliverBatch {
+    const SgDeliverDesc* desc;
+    uint32_t ndesc;
+    const uint8_t* data;
+    const uint64_t* fr_off;
+    const uint64_t* out_off;
+    const uint32_t* in_len;
+    const int32_t* ret;
+    const int32_t* dret;
+    uint32_t max_len;  // upper bound of in_len[] (sizes the grid)
+};
+hipError_t launch_sg_deliver(const SgDeliverBatch& a, hipStream_t stream);
+
 }  // namespace lz4e

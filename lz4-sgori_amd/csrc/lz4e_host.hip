@@ -19,6 +19,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -29,6 +30,7 @@
 
 #include "../../include/lz4e.h"
 #include "lz4e_gpu.h"
+#include "lz4e_hostreg.h"
 #include "lz4e_results.h"
 
 static_assert(lz4e::kDecodeAborted == LZ4E_DECODE_ABORTED, "watchdog return value");
@@ -222,14 +224,20 @@ __global__ __launch_bounds__(256) void copy_flat_kernel(const uint4* __restrict_
         dst[i] = src[i];
 }
 
-hipError_t copy_flat(void* host_dev, const void* dev, uint64_t off, uint64_t n, hipStream_t st) {
+// n bytes from dev + dev_off to host_dev + host_off.
+hipError_t copy_flat(void* host_dev, uint64_t host_off, const void* dev, uint64_t dev_off, uint64_t n,
+                     hipStream_t st) {
     if (n == 0) return hipSuccess;
     const uint64_t n16 = (n + 15) / 16;
     const uint32_t blocks = (uint32_t)std::min<uint64_t>(1024, (n16 + 255) / 256);
     hipLaunchKernelGGL(copy_flat_kernel, dim3(blocks), dim3(256), 0, st,
-                       reinterpret_cast<const uint4*>(static_cast<const uint8_t*>(dev) + off),
-                       reinterpret_cast<uint4*>(static_cast<uint8_t*>(host_dev) + off), n16);
+                       reinterpret_cast<const uint4*>(static_cast<const uint8_t*>(dev) + dev_off),
+                       reinterpret_cast<uint4*>(static_cast<uint8_t*>(host_dev) + host_off), n16);
     return hipGetLastError();
+}
+
+hipError_t copy_flat(void* host_dev, const void* dev, uint64_t off, uint64_t n, hipStream_t st) {
+    return copy_flat(host_dev, off, dev, off, n, st);
 }
 
 // ---------------------------------------------------------------------------
@@ -1012,14 +1020,20 @@ struct ChunkMeta {
 struct ChunkSlot {
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
-    HostBuf h_data, h_meta;
-    DevBuf d_data, d_meta;
+    // h_data stages the slot's staged requests only, [inputs | frames |
+    // outputs]; d_data holds every request's, the staged ones first in each
+    // of its three parts.  h_desc / d_desc: the zero-copy requests' gather
+    // and deliver descriptors (lz4e_gpu.h).
+    HostBuf h_data, h_meta, h_desc;
+    DevBuf d_data, d_meta, d_desc;
     void* h_dev = nullptr;  // h_data as the device sees it
     bool busy = false;
     bool want_frames = false;
     std::vector<uint32_t> req;        // request index per entry
-    std::vector<uint64_t> fr, out;    // frame / output offsets in the data buffer
-    uint64_t in_bytes = 0, fr_bytes = 0, out_bytes = 0;
+    std::vector<uint8_t> zc;          // per entry: the device reads and writes the caller's memory
+    std::vector<uint64_t> fr, out;    // staged entries: frame / output offsets in h_data
+    uint32_t n_zc = 0;
+    uint64_t in_bytes = 0, fr_bytes = 0, out_bytes = 0;  // of the staged entries
     size_t meta_ret = 0, meta_dret = 0;
     // LZ4E_CHUNK_PROF=2: timing events (before H2D, after H2D, compress,
     // decompress, D2H) and host times of the sub-batch's phases
@@ -1106,6 +1120,73 @@ std::atomic<uint64_t> g_chunk_sub_bytes{0};
 // Launch order override per direction (compress, decompress): -1 default.
 std::atomic<int> g_order_override[2] = {{-1}, {-1}};
 
+// Host memory registered with lz4e_register_host_memory.  Lock order:
+// ChunkCtx::mu, then this one.  Registrations are only erased under
+// ChunkCtx::mu, so an address translated inside a chunk call stays valid for
+// the whole call.
+struct HostReg {
+    std::mutex mu;
+    lz4e::HostRegistry map;
+};
+HostReg& host_reg() {
+    static HostReg r;
+    return r;
+}
+
+// Requests whose input the device gathered (lz4e_debug_chunk_zero_copy_requests).
+std::atomic<uint64_t> g_chunk_zero_copy_requests{0};
+
+// Translations of one sub-batch (HostReg::mu held): consecutive pieces
+// mostly lie in the registration of the piece before.
+struct RegView {
+    const lz4e::HostRegistry& reg;
+    const lz4e::HostRegistry::Range* last = nullptr;
+    uint64_t translate(const void* ptr, size_t len) {
+        const uintptr_t p = reinterpret_cast<uintptr_t>(ptr);
+        if (!last || p < last->base || p - last->base >= last->len) last = reg.find(p);
+        return last ? lz4e::HostRegistry::translate_in(*last, p, len) : lz4e::HostRegistry::kNotContained;
+    }
+};
+
+// Path choice of one accepted request: zero-copy only when every source
+// byte the iterator covers, [data, data + len) and (frame set)
+// [frame, frame + frame_cap) each lie wholly inside one live registration.
+// Appends the request's gather descriptors (dst_off relative to its input's
+// start) and fills its deliver descriptor; leaves `gd` as it was otherwise.
+bool plan_zero_copy(RegView& rv, const lz4e_chunk_request& q, uint32_t len,
+                    std::vector<lz4e::SgGatherDesc>& gd, lz4e::SgDeliverDesc& dd) {
+    constexpr uint64_t kNC = lz4e::HostRegistry::kNotContained;
+    dd.data = rv.translate(q.data, len);
+    if (dd.data == kNC) return false;
+    dd.frame = 0;
+    dd.frame_cap = q.frame_cap;
+    if (q.frame) {
+        if (q.frame_cap < 0) return false;
+        dd.frame = rv.translate(q.frame, (size_t)q.frame_cap);
+        if (dd.frame == kNC) return false;
+    }
+    const size_t mark = gd.size();
+    uint32_t idx = q.srcIter->bi_idx, done = q.srcIter->bi_bvec_done, left = len;
+    uint64_t at = 0;
+    while (left) {
+        const uint32_t take = std::min(q.src[idx].bv_len - done, left);
+        if (take) {
+            const uint64_t src = rv.translate(bv_data(q.src[idx]) + done, take);
+            if (src == kNC) {
+                gd.resize(mark);
+                return false;
+            }
+            for (uint32_t p = 0; p < take; p += lz4e::kSgPiece)
+                gd.push_back({src + p, at + p, std::min(take - p, lz4e::kSgPiece), 0});
+        }
+        at += take;
+        left -= take;
+        done = 0;
+        idx++;
+    }
+    return true;
+}
+
 // Waits for a slot's sub-batch and hands its results to the requests;
 // counts into `st` (this call's stats, added to the caller's on success).
 bool chunk_finish(ChunkSlot& s, struct lz4e_chunk_request* reqs, struct lz4e_chunk_stats& st,
@@ -1136,16 +1217,18 @@ bool chunk_finish(ChunkSlot& s, struct lz4e_chunk_request* reqs, struct lz4e_chu
             q.status = kEIO;
             return;
         }
-        if (q.frame) {
-            if (q.frame_cap < ret[j]) {
-                q.status = kENOSPC;
-                return;
-            }
-            std::memcpy(q.frame, hd + s.fr[j], (size_t)ret[j]);
+        if (q.frame && q.frame_cap < ret[j]) {
+            q.status = kENOSPC;
+            return;
         }
-        if (len > 0) std::memcpy(q.data, hd + s.out[j], (size_t)len);
         q.status = 0;
+        // a zero-copy entry: sg_deliver_kernel took the same decision from
+        // the same values and has written frame and data already
+        if (s.zc[j]) return;
+        if (q.frame) std::memcpy(q.frame, hd + s.fr[j], (size_t)ret[j]);
+        if (len > 0) std::memcpy(q.data, hd + s.out[j], (size_t)len);
     });
+    g_chunk_zero_copy_requests.fetch_add(s.n_zc);
     if (pr.on) pr.out += now_ms() - t1;
     if (pr.tl && s.pev[4]) {
         float g[4] = {0, 0, 0, 0};
@@ -1212,6 +1295,60 @@ void lz4e_debug_set_launch_order(int compress_mode, int decompress_mode) {
     g_order_override[1].store(decompress_mode);
 }
 
+// Debug hooks (tests and tools, not part of include/lz4e.h): requests whose
+// input the device gathered so far, and the pinned host bytes the pipeline's
+// slots hold right now (staging, metadata and descriptors).
+uint64_t lz4e_debug_chunk_zero_copy_requests(void) { return g_chunk_zero_copy_requests.load(); }
+uint64_t lz4e_debug_chunk_pinned_bytes(void) {
+    ChunkCtx& cc = chunk_ctx();
+    std::lock_guard<std::mutex> lk(cc.mu);
+    uint64_t b = 0;
+    for (const ChunkSlot& s : cc.slot) b += s.h_data.cap + s.h_meta.cap + s.h_desc.cap;
+    return b;
+}
+
+int lz4e_register_host_memory(void* ptr, size_t len) {
+    g_err.clear();
+    const uintptr_t a = reinterpret_cast<uintptr_t>(ptr);
+    if (!ptr || len == 0 || a % LZ4E_PAGE_SIZE || len % LZ4E_PAGE_SIZE || len - 1 > UINTPTR_MAX - a) {
+        set_err("lz4e_register_host_memory: a non-empty range of whole pages is required");
+        return -22;
+    }
+    HostReg& hr = host_reg();
+    std::lock_guard<std::mutex> lk(hr.mu);
+    if (hr.map.overlaps(a, len)) {
+        set_err("lz4e_register_host_memory: the range overlaps a live registration");
+        return -22;
+    }
+    if (!gate().check()) return -1;
+    if (!hip_ok(hipHostRegister(ptr, len, hipHostRegisterMapped | hipHostRegisterPortable),
+                "hipHostRegister"))
+        return -1;
+    void* dev = nullptr;
+    if (!hip_ok(hipHostGetDevicePointer(&dev, ptr, 0), "hipHostGetDevicePointer") ||
+        !hr.map.insert(a, len, reinterpret_cast<uint64_t>(dev))) {
+        (void)hipHostUnregister(ptr);
+        return -1;
+    }
+    return 0;
+}
+
+int lz4e_unregister_host_memory(void* ptr) {
+    g_err.clear();
+    // the pipeline's lock: no chunk call is in flight, so nothing on the
+    // device still holds an address inside the range
+    std::lock_guard<std::mutex> ck(chunk_ctx().mu);
+    HostReg& hr = host_reg();
+    std::lock_guard<std::mutex> lk(hr.mu);
+    if (!hr.map.erase(reinterpret_cast<uintptr_t>(ptr))) {
+        set_err("lz4e_unregister_host_memory: not the base of a live registration");
+        return -2;
+    }
+    // (erased first: whatever HIP answers, the device is never handed an
+    // address of this range again)
+    return hip_ok(hipHostUnregister(ptr), "hipHostUnregister") ? 0 : -1;
+}
+
 int lz4e_chunk_write_batch(struct lz4e_chunk_request* reqs, int n, struct lz4e_chunk_stats* stats) {
     if (n <= 0) return 0;
     auto fail_all = [&]() {
@@ -1240,11 +1377,16 @@ int lz4e_chunk_write_batch(struct lz4e_chunk_request* reqs, int n, struct lz4e_c
         chunk_drain(cc);
         return fail_all();
     };
-    uint64_t total = 0;
-    for (uint32_t r = 0; r < N; ++r) total += reqs[r].srcIter->bi_size;
+    uint64_t call_bytes = 0;
+    for (uint32_t r = 0; r < N; ++r) call_bytes += reqs[r].srcIter->bi_size;
     const uint64_t forced = g_chunk_sub_bytes.load();
     const uint64_t sub_bytes =
-        forced ? forced : std::min(kSubBytesMax, std::max(kSubBytesMin, (total + kSlots - 1) / kSlots));
+        forced ? forced : std::min(kSubBytesMax, std::max(kSubBytesMin, (call_bytes + kSlots - 1) / kSlots));
+    // LZ4E_CHUNK_ZERO_COPY=0 (read per call): every request staged
+    const char* zenv = getenv("LZ4E_CHUNK_ZERO_COPY");
+    const bool zero_copy = !(zenv && zenv[0] == '0' && zenv[1] == 0);
+    std::vector<lz4e::SgGatherDesc> gdesc;
+    std::vector<lz4e::SgDeliverDesc> ddesc;
     const uint32_t sub_reqs = forced ? kSubReqsMin : std::max(kSubReqsMin, (N + kSlots - 1) / kSlots);
     while (i < N) {
         ChunkSlot& s = cc.slot[k % kSlots];
@@ -1254,54 +1396,99 @@ int lz4e_chunk_write_batch(struct lz4e_chunk_request* reqs, int n, struct lz4e_c
             set_err("lz4e: injected pipeline fault");
             return abort();
         }
-        // ---- form the sub-batch: requests [i, e) ----
+        // ---- form the sub-batch: requests [i, e), each on its path ----
         s.req.clear();
-        s.fr.clear();
-        s.out.clear();
-        std::vector<uint64_t> in;
+        s.zc.clear();
+        gdesc.clear();
+        ddesc.clear();
+        std::vector<uint32_t> lens, gfirst;  // per entry: input bytes, first gather descriptor
         std::vector<uint8_t> tt;
-        uint64_t ib = 0, fb = 0, ob = 0;
+        uint64_t sum_in = 0;
         uint32_t max_len = 0;
-        bool frames = false;
-        for (; i < N && s.req.size() < sub_reqs && (s.req.empty() || ib < sub_bytes); ++i) {
-            const lz4e_chunk_request& q = reqs[i];
-            const uint32_t len = q.srcIter->bi_size;
-            int t = LZ4E_TABLE_BYU16;
-            // compress returns 0 -> -EIO, no stats (lz4e_dev.c:187-202)
-            if (len > LZ4E_MAX_INPUT_SIZE) continue;  // lz4e_compress.c:245-248
-            if (len >= 13 && (t = table_type_of(q.src, q.srcIter)) == 0) continue;  // :274-277
-            s.req.push_back(i);
-            in.push_back(ib);
-            tt.push_back((uint8_t)t);
-            ib += align16(len);
-            s.fr.push_back(fb);
-            fb += align16((uint64_t)bound_of(len) + 64);
-            s.out.push_back(ob);
-            ob += align16((uint64_t)len + 64);
-            max_len = std::max(max_len, len);
-            frames |= q.frame != nullptr;
+        {
+            HostReg& hr = host_reg();
+            std::unique_lock<std::mutex> rk(hr.mu, std::defer_lock);
+            if (zero_copy) rk.lock();
+            RegView rv{hr.map};
+            const bool try_zc = zero_copy && !hr.map.empty();
+            for (; i < N && s.req.size() < sub_reqs && (s.req.empty() || sum_in < sub_bytes); ++i) {
+                const lz4e_chunk_request& q = reqs[i];
+                const uint32_t len = q.srcIter->bi_size;
+                int t = LZ4E_TABLE_BYU16;
+                // compress returns 0 -> -EIO, no stats (lz4e_dev.c:187-202)
+                if (len > LZ4E_MAX_INPUT_SIZE) continue;  // lz4e_compress.c:245-248
+                if (len >= 13 && (t = table_type_of(q.src, q.srcIter)) == 0) continue;  // :274-277
+                lz4e::SgDeliverDesc dd{0, 0, (uint32_t)s.req.size(), 0};
+                gfirst.push_back((uint32_t)gdesc.size());
+                const bool z = try_zc && plan_zero_copy(rv, q, len, gdesc, dd);
+                if (z) ddesc.push_back(dd);
+                s.req.push_back(i);
+                s.zc.push_back(z ? 1 : 0);
+                lens.push_back(len);
+                tt.push_back((uint8_t)t);
+                sum_in += align16(len);
+                max_len = std::max(max_len, len);
+            }
         }
         const uint32_t R = (uint32_t)s.req.size();
         if (R == 0) continue;
-        for (uint32_t j = 0; j < R; ++j) {  // one data buffer: [inputs | frames | outputs]
-            s.fr[j] += ib;
-            s.out[j] += ib + fb;
+        gfirst.push_back((uint32_t)gdesc.size());
+        // One HBM data buffer, [inputs | frames | outputs], in each part the
+        // staged entries first: they are one H2D copy and two copy-backs
+        // whatever else the sub-batch holds, and the pinned staging is those
+        // three runs and nothing more.
+        std::vector<uint64_t> in(R), dfr(R), dout(R);
+        s.fr.assign(R, 0);
+        s.out.assign(R, 0);
+        uint64_t ib = 0, fb = 0, ob = 0, ib_s = 0, fb_s = 0, ob_s = 0;
+        bool frames = false;  // a staged entry wants its frame
+        for (int pass = 0; pass < 2; ++pass) {
+            for (uint32_t j = 0; j < R; ++j) {
+                if (s.zc[j] != pass) continue;
+                in[j] = ib;
+                ib += align16(lens[j]);
+                dfr[j] = fb;
+                fb += align16((uint64_t)bound_of(lens[j]) + 64);
+                dout[j] = ob;
+                ob += align16((uint64_t)lens[j] + 64);
+                if (pass == 0) frames |= reqs[s.req[j]].frame != nullptr;
+            }
+            if (pass == 0) ib_s = ib, fb_s = fb, ob_s = ob;
         }
-        s.in_bytes = ib;
-        s.fr_bytes = fb;
-        s.out_bytes = ob;
+        for (uint32_t j = 0; j < R; ++j) {
+            s.fr[j] = ib_s + dfr[j];  // in h_data (staged entries)
+            s.out[j] = ib_s + fb_s + dout[j];
+            dfr[j] += ib;             // in d_data
+            dout[j] += ib + fb;
+            if (s.zc[j])
+                for (uint32_t g = gfirst[j]; g < gfirst[j + 1]; ++g) gdesc[g].dst_off += in[j];
+        }
+        s.n_zc = (uint32_t)ddesc.size();
+        s.in_bytes = ib_s;
+        s.fr_bytes = fb_s;
+        s.out_bytes = ob_s;
         s.want_frames = frames;
         const ChunkMeta m(R);
-        const uint64_t total = ib + fb + ob;
-        if (!s.h_data.ensure(total) || !s.d_data.ensure(total) || !s.h_meta.ensure(m.total) ||
-            !s.d_meta.ensure(m.total) ||
-            !hip_ok(hipHostGetDevicePointer(&s.h_dev, s.h_data.p, 0), "hipHostGetDevicePointer"))
+        const uint64_t slot_bytes = ib + fb + ob, staged_bytes = ib_s + fb_s + ob_s;
+        const size_t gd_bytes = align16(gdesc.size() * sizeof(lz4e::SgGatherDesc)),
+                     desc_bytes = gd_bytes + ddesc.size() * sizeof(lz4e::SgDeliverDesc);
+        if (!s.h_data.ensure(staged_bytes) || !s.d_data.ensure(slot_bytes) || !s.h_meta.ensure(m.total) ||
+            !s.d_meta.ensure(m.total) || !s.h_desc.ensure(desc_bytes) || !s.d_desc.ensure(desc_bytes) ||
+            (s.h_data.p &&
+             !hip_ok(hipHostGetDevicePointer(&s.h_dev, s.h_data.p, 0), "hipHostGetDevicePointer")))
             return abort();
         uint8_t* hd = static_cast<uint8_t*>(s.h_data.p);
         uint8_t* hm = static_cast<uint8_t*>(s.h_meta.p);
-        // ---- gather (overlaps the other slots' GPU work) ----
+        if (desc_bytes) {
+            uint8_t* hq = static_cast<uint8_t*>(s.h_desc.p);
+            if (!gdesc.empty()) std::memcpy(hq, gdesc.data(), gdesc.size() * sizeof(lz4e::SgGatherDesc));
+            if (!ddesc.empty())
+                std::memcpy(hq + gd_bytes, ddesc.data(), ddesc.size() * sizeof(lz4e::SgDeliverDesc));
+        }
+        // ---- gather of the staged entries (overlaps the other slots' GPU work) ----
         const double tg = pr.on ? now_ms() : 0;
-        par_for(R, ib, [&](uint32_t j) {
+        par_for(R, ib_s, [&](uint32_t j) {
+            if (s.zc[j]) return;
             const lz4e_chunk_request& q = reqs[s.req[j]];
             sg_gather(q.src, *q.srcIter, hd + in[j], q.srcIter->bi_size);
         });
@@ -1322,9 +1509,9 @@ int lz4e_chunk_write_batch(struct lz4e_chunk_request* reqs, int n, struct lz4e_c
             reinterpret_cast<uint64_t*>(hm + m.in_off)[j] = in[j];
             reinterpret_cast<uint32_t*>(hm + m.in_len)[j] = len;
             (hm + m.ttype)[j] = tt[j];
-            reinterpret_cast<uint64_t*>(hm + m.fr_off)[j] = s.fr[j];
+            reinterpret_cast<uint64_t*>(hm + m.fr_off)[j] = dfr[j];
             reinterpret_cast<uint32_t*>(hm + m.fr_cap)[j] = bound_of(len);  // dst_buf.buf_size
-            reinterpret_cast<uint64_t*>(hm + m.out_off)[j] = s.out[j];
+            reinterpret_cast<uint64_t*>(hm + m.out_off)[j] = dout[j];
             reinterpret_cast<int32_t*>(hm + m.out_cap)[j] = (int32_t)len;  // src_buf.buf_size
         }
         s.meta_ret = m.ret;
@@ -1352,11 +1539,27 @@ int lz4e_chunk_write_batch(struct lz4e_chunk_request* reqs, int n, struct lz4e_c
                                        reinterpret_cast<int32_t*>(dm + m.dret),
                                        R,
                                        max_len};
+        // the zero-copy entries: the device fetches their segments itself and
+        // takes chunk_finish's decision on what reaches the caller
+        uint8_t* dq = static_cast<uint8_t*>(s.d_desc.p);
+        const lz4e::SgDeliverBatch sa{reinterpret_cast<const lz4e::SgDeliverDesc*>(dq + gd_bytes),
+                                      (uint32_t)ddesc.size(),
+                                      dd,
+                                      reinterpret_cast<const uint64_t*>(dm + m.fr_off),
+                                      reinterpret_cast<const uint64_t*>(dm + m.out_off),
+                                      reinterpret_cast<const uint32_t*>(dm + m.in_len),
+                                      reinterpret_cast<const int32_t*>(dm + m.ret),
+                                      reinterpret_cast<const int32_t*>(dm + m.dret),
+                                      max_len};
         // from here on the slot has work in flight: a failure must drain it
         s.busy = true;
         mark(0);
-        if (!hip_ok(hipMemcpyAsync(dd, hd, ib, hipMemcpyHostToDevice, s.stream), "H2D data") ||
-            !hip_ok(hipMemcpyAsync(dm, hm, m.ret, hipMemcpyHostToDevice, s.stream), "H2D meta"))
+        if ((ib_s && !hip_ok(hipMemcpyAsync(dd, hd, ib_s, hipMemcpyHostToDevice, s.stream), "H2D data")) ||
+            !hip_ok(hipMemcpyAsync(dm, hm, m.ret, hipMemcpyHostToDevice, s.stream), "H2D meta") ||
+            (desc_bytes && !hip_ok(hipMemcpyAsync(dq, s.h_desc.p, desc_bytes, hipMemcpyHostToDevice,
+                                                  s.stream), "H2D descriptors")) ||
+            !hip_ok(lz4e::launch_sg_gather(reinterpret_cast<const lz4e::SgGatherDesc*>(dq),
+                                           (uint32_t)gdesc.size(), dd, s.stream), "gather launch"))
             return abort();
         mark(1);
         if (!hip_ok(lz4e::launch_compress(ca, s.stream), "compress launch")) return abort();
@@ -1365,8 +1568,9 @@ int lz4e_chunk_write_batch(struct lz4e_chunk_request* reqs, int n, struct lz4e_c
         mark(3);
         if (!hip_ok(hipMemcpyAsync(hm + m.ret, dm + m.ret, m.total - m.ret, hipMemcpyDeviceToHost,
                                    s.stream), "D2H meta") ||
-            (frames && !hip_ok(copy_flat(s.h_dev, dd, ib, fb, s.stream), "D2H frames")) ||
-            !hip_ok(copy_flat(s.h_dev, dd, ib + fb, ob, s.stream), "D2H data"))
+            !hip_ok(lz4e::launch_sg_deliver(sa, s.stream), "deliver launch") ||
+            (frames && !hip_ok(copy_flat(s.h_dev, ib_s, dd, ib, fb_s, s.stream), "D2H frames")) ||
+            !hip_ok(copy_flat(s.h_dev, ib_s + fb_s, dd, ib + fb, ob_s, s.stream), "D2H data"))
             return abort();
         mark(4);
         if (!hip_ok(hipEventRecord(s.done, s.stream), "event record")) return abort();

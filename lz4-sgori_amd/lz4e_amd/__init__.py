@@ -30,7 +30,8 @@ __all__ = [
     "SgRequest", "SgList", "make_sg", "lib", "gpu_available", "table_type",
     "compress_default", "decompress_safe", "compress_sg_batch",
     "decompress_batch", "compress_batch_dev", "decompress_batch_dev",
-    "GpuUnavailable", "LIB_PATH", "EXPORTED_SYMBOLS",
+    "GpuUnavailable", "LIB_PATH", "EXPORTED_SYMBOLS", "HostArena", "GuardReport",
+    "register_host_memory", "unregister_host_memory", "zero_copy_requests",
 ]
 
 PAGE_SIZE = 4096
@@ -50,6 +51,7 @@ EXPORTED_SYMBOLS = (
     "lz4e_chunk_write_batch", "lz4e_decompress_safe_sg", "lz4e_decompress_sg_batch",
     "LZ4E_compress_usingDict", "LZ4E_decompress_safe_usingDict", "lz4e_compress_sg_batch_dict",
     "lz4e_decompress_batch_dict", "lz4e_compress_batch_dev_dict", "lz4e_decompress_batch_dev_dict",
+    "lz4e_register_host_memory", "lz4e_unregister_host_memory",
 )
 
 
@@ -158,6 +160,15 @@ def lib() -> ctypes.CDLL:
     L.lz4e_compress_batch_dev_dict.restype = I32
     L.lz4e_decompress_batch_dev_dict.argtypes = [P, P, P, P, P, P, P, U32, U32, P, P]
     L.lz4e_decompress_batch_dev_dict.restype = I32
+    # (LZ4E_LIB may name an older build for an A/B run, tools/e2e.py: it
+    # lacks these three, and using them then fails with AttributeError)
+    if hasattr(L, "lz4e_register_host_memory"):
+        L.lz4e_register_host_memory.argtypes = [P, ctypes.c_size_t]
+        L.lz4e_register_host_memory.restype = I32
+        L.lz4e_unregister_host_memory.argtypes = [P]
+        L.lz4e_unregister_host_memory.restype = I32
+        L.lz4e_debug_chunk_zero_copy_requests.argtypes = []
+        L.lz4e_debug_chunk_zero_copy_requests.restype = ctypes.c_uint64
     _lib = L
     return L
 
@@ -214,9 +225,70 @@ class SgList:
         return bytes(out[:n])
 
 
+EINVAL, ENOENT = 22, 2
+
+
+def register_host_memory(addr: int, nbytes: int) -> int:
+    """lz4e_register_host_memory: 0, -22 (bad argument) or -1 (no GPU / HIP refused)."""
+    return lib().lz4e_register_host_memory(addr, nbytes)
+
+
+def unregister_host_memory(addr: int) -> int:
+    """lz4e_unregister_host_memory: 0, -2 (not a registration's base) or -1."""
+    return lib().lz4e_unregister_host_memory(addr)
+
+
+def zero_copy_requests() -> int:
+    """lz4e_debug_chunk_zero_copy_requests: chunk requests whose input the device gathered so far."""
+    return int(lib().lz4e_debug_chunk_zero_copy_requests())
+
+
+class HostArena:
+    """A page-aligned host buffer, registered with the library while the
+    ``with`` block runs (lz4e_register_host_memory on entry,
+    lz4e_unregister_host_memory on exit) and handed out piecewise by
+    :meth:`alloc`.  The memory exists from construction on, so the same
+    buffers can be used before, inside and after the registration."""
+
+    def __init__(self, nbytes: int):
+        self.size = max(1, -(-int(nbytes) // PAGE_SIZE)) * PAGE_SIZE
+        self._raw = np.zeros(self.size + PAGE_SIZE, dtype=np.uint8)
+        start = -self._raw.ctypes.data % PAGE_SIZE
+        self.buf = self._raw[start:start + self.size]
+        self.base = self.buf.ctypes.data
+        self.used = 0
+        self.registered = False
+
+    def alloc(self, nbytes: int, align: int = 16) -> np.ndarray:
+        """The next ``nbytes`` of the arena at a multiple of ``align`` (a uint8 view)."""
+        at = -(-(self.base + self.used) // align) * align - self.base
+        if at + nbytes > self.size:
+            raise MemoryError(f"HostArena: {nbytes} bytes asked, {self.size - at} left")
+        self.used = at + nbytes
+        return self.buf[at:at + nbytes]
+
+    def reset(self) -> None:
+        self.used = 0
+
+    def __enter__(self) -> "HostArena":
+        r = register_host_memory(self.base, self.size)
+        if r == -EINVAL:
+            raise ValueError("lz4e_register_host_memory: " + last_error())
+        if r != 0:
+            raise GpuUnavailable(last_error() or "lz4e_register_host_memory failed")
+        self.registered = True
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.registered = False
+        r = unregister_host_memory(self.base)
+        if r != 0 and exc[0] is None:
+            raise RuntimeError(f"lz4e_unregister_host_memory: {r} {last_error()}")
+
+
 def make_sg(data: bytes, segments: Sequence[int], offsets: Optional[Sequence[int]] = None,
             start_done: int = 0, capacity: Optional[int] = None, shuffle_seed: Optional[int] = None,
-            fill: int = 0) -> SgList:
+            fill: int = 0, arena: Optional[HostArena] = None) -> SgList:
     """Build a bio_vec list whose segments have the given lengths.
 
     Segment i lives at in-page offset offsets[i] (default 0) on its own run of
@@ -224,7 +296,8 @@ def make_sg(data: bytes, segments: Sequence[int], offsets: Optional[Sequence[int
     runs are placed in a shuffled order, so consecutive segments are not
     adjacent in memory.  ``data`` is written across the segments starting at
     byte ``start_done`` of segment 0; the iterator covers ``len(data)`` bytes
-    (or ``capacity`` bytes for a destination list).
+    (or ``capacity`` bytes for a destination list).  With ``arena`` the pages
+    come out of that :class:`HostArena` instead of fresh numpy memory.
     """
     segments = list(segments)
     offsets = list(offsets) if offsets is not None else [0] * len(segments)
@@ -238,7 +311,11 @@ def make_sg(data: bytes, segments: Sequence[int], offsets: Optional[Sequence[int
     for i in order:
         start_page[i] = p
         p += runs[i]
-    raw = np.full((p + 1) * PAGE_SIZE, fill, dtype=np.uint8)
+    if arena is not None:
+        raw = arena.alloc(max(1, p) * PAGE_SIZE, PAGE_SIZE)
+        raw[:] = fill
+    else:
+        raw = np.full((p + 1) * PAGE_SIZE, fill, dtype=np.uint8)
     base = raw.ctypes.data
     aligned = (base + PAGE_SIZE - 1) // PAGE_SIZE * PAGE_SIZE
     bvecs = (BioVec * max(1, len(segments)))()
@@ -411,36 +488,104 @@ def decompress_sg_batch(frames: Sequence[bytes], dsts: Sequence[SgList]) -> List
     return list(rt)
 
 
+@dataclass
+class GuardReport:
+    """What chunk_write_batch(guard=G) saw around its buffers after the call:
+    ``intact`` -- every guard byte on both sides of every data and frame
+    buffer still holds the guard pattern; ``bad`` -- indices of the requests
+    with a damaged guard; ``untouched[i]`` -- request i's data and frame
+    buffers still hold their pre-call fill in every byte."""
+    intact: bool
+    bad: List[int]
+    untouched: List[bool]
+
+
+_GUARD_BYTE, _FILL_BYTE = 0xA5, 0x5A
+
+
 def chunk_write_batch(srcs: Sequence[SgList], want_frames: bool = False,
-                      stats: Optional[ChunkStats] = None):
+                      stats: Optional[ChunkStats] = None, arena=None,
+                      frame_caps: Optional[Sequence[Optional[int]]] = None, guard: int = 0):
     """lz4e_chunk_write_batch over WRITE bios given as SG lists.
 
     Returns (good, [(status, comp_size, data bytes, frame bytes or None)]),
-    the chunk layer's result per request (lz4e_bdev/lz4e_req.c:144-213)."""
+    the chunk layer's result per request (lz4e_bdev/lz4e_req.c:144-213).
+
+    ``arena``: the data and frame buffers come out of that HostArena (at byte
+    granularity, so at every alignment) instead of fresh memory; a list
+    gives each request its own choice: a HostArena, None (fresh memory), or a
+    pair (arena of the data buffer, arena of the frame buffer).
+    ``frame_caps``: per-request frame capacity (None: LZ4E_COMPRESSBOUND);
+    giving it asks for frames like ``want_frames``.  ``guard`` > 0: every
+    buffer is pre-filled with a pattern and sits between two runs of
+    ``guard`` bytes of another, and a :class:`GuardReport` is returned as a
+    third value."""
     _require_gpu()
     n = len(srcs)
     reqs = (ChunkRequest * max(1, n))()
-    datas, frames = [], []
+    want_frames = want_frames or frame_caps is not None
+
+    def arenas_of(i):
+        a = arena[i] if isinstance(arena, list) else arena
+        return a if isinstance(a, tuple) else (a, a)
+
+    def buffer(size, arena):
+        """(keep-alive object, whole array incl. guards or None, address of the payload)"""
+        if arena is None and guard == 0:
+            b = ctypes.create_string_buffer(max(1, size))
+            return b, None, ctypes.addressof(b)
+        total = max(1, size + 2 * guard)
+        a = arena.alloc(total, 1) if arena is not None else np.empty(total, np.uint8)
+        a[:] = _GUARD_BYTE if guard else 0
+        if guard:
+            a[guard:guard + size] = _FILL_BYTE
+        return a, a, a.ctypes.data + guard
+
+    datas, frames, caps = [], [], []
     for i, s in enumerate(srcs):
         size = s.it.bi_size
-        d = ctypes.create_string_buffer(max(1, size))
-        f = ctypes.create_string_buffer(max(1, compress_bound(size))) if want_frames else None
+        cap = compress_bound(size)
+        if frame_caps is not None and frame_caps[i] is not None:
+            cap = int(frame_caps[i])
+        d_arena, f_arena = arenas_of(i)
+        d = buffer(size, d_arena)
+        f = buffer(cap, f_arena) if want_frames else None
         datas.append(d)
         frames.append(f)
+        caps.append(cap)
         reqs[i].src = s.bvecs
         reqs[i].srcIter = ctypes.pointer(s.it)
-        reqs[i].data = ctypes.addressof(d)
-        reqs[i].frame = ctypes.addressof(f) if f is not None else None
-        reqs[i].frame_cap = compress_bound(size) if f is not None else 0
+        reqs[i].data = d[2]
+        reqs[i].frame = f[2] if f is not None else None
+        reqs[i].frame_cap = cap if f is not None else 0
     good = lib().lz4e_chunk_write_batch(reqs, n, ctypes.byref(stats) if stats is not None else None)
     if good < 0:
         raise GpuUnavailable(last_error())
+
+    def payload(b, size, k):
+        return ctypes.string_at(b[2], min(k, size)) if size else b""
+
     out = []
     for i, s in enumerate(srcs):
         r = reqs[i]
-        fr = frames[i].raw[:r.comp_size] if frames[i] is not None and r.status == 0 else None
-        out.append((r.status, r.comp_size, datas[i].raw[:s.it.bi_size] if r.status == 0 else None, fr))
-    return good, out
+        fr = payload(frames[i], caps[i], r.comp_size) if frames[i] is not None and r.status == 0 else None
+        out.append((r.status, r.comp_size,
+                    payload(datas[i], s.it.bi_size, s.it.bi_size) if r.status == 0 else None, fr))
+    if not guard:
+        return good, out
+    bad, untouched = [], []
+    for i, s in enumerate(srcs):
+        ok, clean = True, True
+        for b, size in ((datas[i], s.it.bi_size), (frames[i], caps[i])):
+            if b is None:
+                continue
+            a = b[1]
+            ok &= bool((a[:guard] == _GUARD_BYTE).all() and (a[guard + size:] == _GUARD_BYTE).all())
+            clean &= bool((a[guard:guard + size] == _FILL_BYTE).all())
+        if not ok:
+            bad.append(i)
+        untouched.append(clean)
+    return good, out, GuardReport(not bad, bad, untouched)
 
 
 # ---------------------------------------------------------------------------

@@ -5,6 +5,8 @@
 # builtins come from tools/emu/include/hip/hip_runtime.h).
 #   tools/emu/build.sh [flags...]        -> $EMU_BUILD/libemu.so (default tools/emu/build)
 #   EMU_EXE=1 tools/emu/build.sh [flags] -> $EMU_BUILD/emu_main (standalone)
+#   EMU_SG=1 tools/emu/build.sh [flags]  -> $EMU_BUILD/emu_sg (standalone: the
+#                                           zero-copy kernels of csrc/lz4e_sg.hip)
 # Pass extra flags, e.g. -fsanitize=address,undefined or -DLZ4E_SPIN_MAX=1.
 set -e
 here=$(cd "$(dirname "$0")" && pwd)
@@ -13,7 +15,10 @@ b="${EMU_BUILD:-$here/build}"
 mkdir -p "$b"
 CXX=${CXX:-/opt/rocm/llvm/bin/clang++}
 FLAGS=(-std=c++20 -O1 -g -pthread -x c++ -DLZ4E_EMU -I "$here/include" -I "$csrc")
-if [ -n "$EMU_EXE" ]; then
+if [ -n "$EMU_SG" ]; then
+    $CXX "${FLAGS[@]}" -I "$here/../../include" "$@" "$here/emu_sg.cpp" -o "$b/emu_sg"
+    echo "built $b/emu_sg"
+elif [ -n "$EMU_EXE" ]; then
     $CXX "${FLAGS[@]}" "$@" "$here/emu.cpp" "$here/emu_dec.cpp" "$here/emu_main.cpp" -o "$b/emu_main"
     echo "built $b/emu_main"
 else
