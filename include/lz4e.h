@@ -25,6 +25,24 @@
  * The batched lz4e_*_batch_* entry points are the throughput path: many
  * independent blocks per launch, device-resident buffers, caller's stream.
  *
+ * Placement contract of the device-resident entry points
+ * (lz4e_compress_batch_dev, lz4e_decompress_batch_dev2 / _dev and their
+ * _dict forms):
+ *   - src_off[i] and dst_off[i] need no alignment; blocks may sit at any
+ *     byte address, packed back to back.
+ *   - Reads stay inside the aligned 4-byte words that hold block i's input
+ *     bytes (and its dictionary's): at most 3 bytes before the first and
+ *     3 bytes after the last byte.
+ *   - Writes stay inside [dst_off[i], dst_off[i] + dst_cap[i]): no slack is
+ *     needed after a slot, and a block that fails (compress returns 0,
+ *     decompress a negative value) writes nowhere else either.  Bytes of a
+ *     slot past the returned size are unspecified.
+ * Evidence: tests/test_gpu_placement.py runs every residue mod 16 on the GPU
+ * with every byte outside the slots checked (values and the write bullet; a
+ * GPU test cannot observe reads).  The read bullet rests on the lane
+ * emulator: tools/emu/emu_main --skew S,D runs the kernels' sources on
+ * exactly sized, poisoned buffers under ASan (tests/test_emulator.py).
+ *
  * Plain C, no torch types.  All sizes are bytes.
  */
 #ifndef LZ4E_AMD_H

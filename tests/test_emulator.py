@@ -21,6 +21,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import frame_synth
 import oracle_ref
 from lz4e_amd import BYU16, BYU32, BYU64, corpus
 
@@ -129,13 +130,14 @@ def test_emulated_kernel_dictionary_sanitized(emu_exe, tmp_path, kind, n, dsize)
 # dictionary or a write past the capacity is caught
 # ---------------------------------------------------------------------------
 
-def _emu_decode(exe, tmp_path, frame, cap, dic=b"", flag="-d"):
+def _emu_decode(exe, tmp_path, frame, cap, dic=b"", flag="-d", skew=None):
     f, o, d = tmp_path / "f.bin", tmp_path / "o.bin", tmp_path / "d.bin"
     f.write_bytes(frame)
     d.write_bytes(dic)
     if o.exists():
         o.unlink()
-    out = subprocess.run([exe, flag, str(f), str(cap), str(o), str(d)], capture_output=True, text=True,
+    pre = ["--skew", "%d,%d" % skew] if skew else []
+    out = subprocess.run([exe, *pre, flag, str(f), str(cap), str(o), str(d)], capture_output=True, text=True,
                          timeout=1200)
     assert out.returncode == 0, out.stderr[-2000:]
     assert "ERROR: AddressSanitizer" not in out.stderr and "runtime error" not in out.stderr
@@ -455,3 +457,75 @@ def test_emulated_pipe_decoder_watchdog(emu_exe_spin1, tmp_path, flag):
     assert r == -2**31
     good, msg = res.split(" ", 2)[1:]
     assert int(good) == -1 and "watchdog" in msg and "LZ4E_DECODE_ABORTED" in msg
+
+
+# ---------------------------------------------------------------------------
+# Unaligned placements and frames no LZ4E encoder emits (tests/frame_synth.py)
+# on the emulator: emu_main --skew S,D puts the input S and the output D bytes
+# past a 16-byte boundary in buffers that still end exactly where the block
+# does.  The subset is sized for one to one and a half minutes of emulator
+# time (measured 51-66 s); the GPU
+# suite runs the full sets (test_gpu_placement.py, test_gpu_foreign_frames.py).
+# ---------------------------------------------------------------------------
+
+ALL_DECODERS = ["-d", "-p", "-l", "-g", "-G"]
+SKEW_PAIRS = [(1, 3), (6, 15), (15, 9), (8, 2)]
+
+
+@pytest.mark.parametrize("skew", SKEW_PAIRS, ids=[f"s{s}-d{d}" for s, d in SKEW_PAIRS])
+def test_emulated_skewed_placement(emu_exe, tmp_path, skew):
+    """One small block at a source and a destination off the 16-byte grid:
+    compress in both table classes (LDS-staged: stage_block's byte loop, the
+    word-aligned window base) and the five decoders on its frame, exact
+    capacity and a short one, against the oracle."""
+    data = _block("text", 1500, 41).tobytes()
+    blk, frame = tmp_path / "blk.bin", tmp_path / "frame.bin"
+    blk.write_bytes(data)
+    for cls in (BYU16, BYU32):
+        out = subprocess.run([emu_exe, "--skew", "%d,%d" % skew, str(blk), str(cls), str(frame)],
+                             capture_output=True, text=True, timeout=1200)
+        assert out.returncode == 0, out.stderr[-2000:]
+        assert "ERROR: AddressSanitizer" not in out.stderr and "runtime error" not in out.stderr
+        _, r, _, fs, lr = out.stdout.split()
+        er, ef, efs, elr = oracle_ref.compress(data, cls)
+        assert (int(r), int(fs), int(lr)) == (er, efs, elr)
+        assert frame.read_bytes() == ef
+    for flag in ALL_DECODERS:
+        for cap in (len(data), len(data) - 7):
+            want = oracle_ref.decompress(ef, cap)
+            got = _emu_decode(emu_exe, tmp_path, ef, cap, flag=flag, skew=skew)
+            assert got[0] == want[0], (flag, cap, got[0], want[0])
+            if want[0] >= 0:
+                assert got[1] == want[1], (flag, cap)
+
+
+def _synth_subset(profile):
+    cs = frame_synth.cases(profile)
+    if profile == "ends":
+        pick = ["ends-l0-m4-c0", "ends-l4-m12-c32", "ends-l5-m7-c0", "ends-l5-m6-c12", "ends-l13-m4-c1"]
+    elif profile == "invalid":
+        pick = ["invalid-offset-k0", "invalid-offset-k63", "invalid-offset-k64", "invalid-twin-offset-k64",
+                "invalid-literal-ext-cut-255", "invalid-match-past-cap-68-6"]
+    elif profile == "dict":
+        pick = ["dict-5-300", "dict-100-300-before", "dict-4096-2000", "dict-65536-300"]
+    else:
+        pick = [c.label for c in cs if c.label.endswith("-0")]  # one of each size
+    by = {c.label: c for c in cs}
+    return [by[k] for k in pick]
+
+
+@pytest.mark.parametrize("profile", sorted(frame_synth.PROFILES))
+def test_emulated_decoders_on_synthesized_frames(emu_exe, tmp_path, profile):
+    """A handful of each profile's frames through the five decoders at
+    rotating skews: values and bytes equal the oracle's."""
+    k = 0
+    for c in _synth_subset(profile):
+        want = oracle_ref.decompress_dict(c.frame, c.cap, c.dic)
+        assert (want[0] >= 0) == c.must_accept or profile == "ends", c.label
+        for flag in ALL_DECODERS:
+            skew = (k % 16, (5 * k + 3) % 16)
+            k += 1
+            got = _emu_decode(emu_exe, tmp_path, c.frame, c.cap, c.dic, flag, skew=skew)
+            assert got[0] == want[0], (c.label, flag, skew, got[0], want[0])
+            if want[0] >= 0:
+                assert got[1] == want[1], (c.label, flag, skew)

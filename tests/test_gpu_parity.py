@@ -11,7 +11,9 @@ import os
 import numpy as np
 import pytest
 
+import gpu_batch
 import oracle_ref
+from gpu_batch import DEC_AUTO, DEC_GROUP, DEC_GROUP_NB, DEC_PIPE, DEC_SMALL, DEC_WAVE
 from lz4e_amd import BYU16, BYU32, BYU64, compress_bound, corpus, make_sg
 
 pytestmark = pytest.mark.gpu
@@ -42,77 +44,15 @@ def _corpus(kind, n, seed):
 # ---------------------------------------------------------------------------
 
 def _gpu_compress(amd, blocks, ttypes, caps=None):
-    import torch
-    n = len(blocks)
-    lens = np.array([len(b) for b in blocks], dtype=np.int64)
-    offs = np.zeros(n, dtype=np.int64)
-    offs[1:] = np.cumsum((lens + 15) // 16 * 16)[:-1]
-    total = int(offs[-1] + lens[-1]) + 16 if n else 16
-    host = np.zeros(total, dtype=np.uint8)
-    for i, b in enumerate(blocks):
-        host[offs[i]:offs[i] + lens[i]] = np.frombuffer(bytes(b), dtype=np.uint8)
-    bounds = lens + lens // 255 + 16
-    caps = bounds if caps is None else np.asarray(caps, dtype=np.int64)
-    slot = np.minimum(caps, bounds) + 64
-    doffs = np.zeros(n, dtype=np.int64)
-    doffs[1:] = np.cumsum((slot + 15) // 16 * 16)[:-1]
-    dev = torch.device("cuda")
-    src = torch.from_numpy(host).to(dev)
-    dst = torch.zeros(int(doffs[-1] + slot[-1]) + 16, dtype=torch.uint8, device=dev)
-    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt)).to(dev)
-    ret = torch.full((n,), -7, dtype=torch.int32, device=dev)
-    aux = torch.zeros(2 * n, dtype=torch.int32, device=dev)
-    amd.compress_batch_dev(src, t(offs, np.int64), t(lens, np.int32), t(ttypes, np.uint8), dst,
-                           t(doffs, np.int64), t(caps, np.int32), ret, aux)
-    torch.cuda.synchronize()
-    r = ret.cpu().numpy()
-    d = dst.cpu().numpy()
-    ax = aux.cpu().numpy().reshape(-1, 2)
-    frames = [d[doffs[i]:doffs[i] + max(r[i], 0)].tobytes() for i in range(n)]
-    return r, frames, ax
-
-
-DEC_AUTO, DEC_WAVE, DEC_PIPE, DEC_SMALL, DEC_GROUP = 0, 1, 2, 6, 7
-DEC_GROUP_NB = 9  # the group decoder without its hand-over (every block decoded by its group)
+    """16-byte aligned placement, guards on (tests/gpu_batch.py)."""
+    return gpu_batch.compress(amd, blocks, ttypes, caps)
 
 
 def _gpu_decompress(amd, frames, caps, csizes=None, max_cap=None, mode=DEC_AUTO):
     """Decode on the GPU; mode forces a decoder (one wave per block, or the
-    pipelined 4-wave one) through the diagnostic entry point."""
-    import torch
-    n = len(frames)
-    csizes = [len(f) for f in frames] if csizes is None else csizes
-    flen = np.array([len(f) for f in frames], dtype=np.int64)
-    offs = np.zeros(n, dtype=np.int64)
-    offs[1:] = np.cumsum((flen + 15) // 16 * 16 + 16)[:-1]
-    host = np.zeros(int(offs[-1] + flen[-1]) + 16 if n else 16, dtype=np.uint8)
-    for i, f in enumerate(frames):
-        host[offs[i]:offs[i] + flen[i]] = np.frombuffer(bytes(f), dtype=np.uint8)
-    caps = np.asarray(caps, dtype=np.int64)
-    slot = np.maximum(caps, 0) + 64
-    doffs = np.zeros(n, dtype=np.int64)
-    doffs[1:] = np.cumsum((slot + 15) // 16 * 16)[:-1]
-    dev = torch.device("cuda")
-    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt)).to(dev)
-    src = torch.from_numpy(host).to(dev)
-    dst = torch.zeros(int(doffs[-1] + slot[-1]) + 16, dtype=torch.uint8, device=dev)
-    ret = torch.full((n,), -7777, dtype=torch.int32, device=dev)
-    if mode == DEC_AUTO:
-        amd.decompress_batch_dev(src, t(offs, np.int64), t(csizes, np.int32), dst, t(doffs, np.int64),
-                                 t(caps, np.int32), ret, max_cap=max_cap)
-    else:
-        L = amd.lib()
-        P = ctypes.c_void_p
-        L.lz4e_debug_decompress_stamped.argtypes = [P] * 7 + [ctypes.c_uint32, P, P, ctypes.c_uint32,
-                                                               ctypes.c_uint32]
-        a = [t(offs, np.int64), t(csizes, np.int32), t(doffs, np.int64), t(caps, np.int32)]
-        assert L.lz4e_debug_decompress_stamped(src.data_ptr(), a[0].data_ptr(), a[1].data_ptr(),
-                                               dst.data_ptr(), a[2].data_ptr(), a[3].data_ptr(),
-                                               ret.data_ptr(), n, None, None, 0, mode) == 0
-    torch.cuda.synchronize()
-    r = ret.cpu().numpy()
-    d = dst.cpu().numpy()
-    return r, [d[doffs[i]:doffs[i] + max(r[i], 0)].tobytes() for i in range(n)]
+    pipelined 4-wave one) through the diagnostic entry point.  16-byte
+    aligned placement, guards on."""
+    return gpu_batch.decompress(amd, frames, caps, csizes, max_cap, mode)
 
 
 # ---------------------------------------------------------------------------
@@ -452,7 +392,8 @@ def test_pipe_decoder_watchdog_valid_worst_case(gpu):
     clen = torch.tensor([len(frames[i % 4]) for i in range(n)], dtype=torch.int32, device=dev)
     doff = torch.arange(n, dtype=torch.int64, device=dev) * bs
     caps = torch.full((n,), bs, dtype=torch.int32, device=dev)
-    out = torch.zeros(n * bs + 64, dtype=torch.uint8, device=dev)
+    image = gpu_batch.device_pattern(n * bs + 64, dev)
+    out = image.clone()
     ret = torch.full((n,), -7777, dtype=torch.int32, device=dev)
     L = gpu.lib()
     P = ctypes.c_void_p
@@ -462,6 +403,7 @@ def test_pipe_decoder_watchdog_valid_worst_case(gpu):
                                            bs, DEC_PIPE) == 0
     torch.cuda.synchronize()
     assert (ret == bs).all(), ret[ret != bs][:8].tolist()
+    gpu_batch.check_guards_strided(out, image, bs, [bs] * n, "decompress[pipe]")
     want = [torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev) for b in srcs]
     for i in range(n):
         assert torch.equal(out[i * bs:(i + 1) * bs], want[i % 4]), i
@@ -732,11 +674,12 @@ def _full_size(gpu, host, lens, bs, cls):
     dev = torch.device("cuda")
     t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt)).to(dev)
     d_src = torch.from_numpy(host).to(dev)
-    d_dst = torch.zeros(n * slot, dtype=torch.uint8, device=dev)
+    image = gpu_batch.device_pattern(n * slot, dev)
+    d_dst = image.clone()
     ret = torch.zeros(n, dtype=torch.int32, device=dev)
     gpu.compress_batch_dev(d_src, t(offs, np.int64), t(lens, np.int32), t(np.full(n, cls), np.uint8),
                            d_dst, t(doffs, np.int64), t(caps, np.int32), ret, max_len=bs)
-    d_out = torch.zeros(n * bs + 64, dtype=torch.uint8, device=dev)
+    d_out = image[:n * bs + 64].clone()
     dret = torch.zeros(n, dtype=torch.int32, device=dev)
     gpu.decompress_batch_dev(d_dst, t(doffs, np.int64), ret, d_out, t(offs, np.int64), t(lens, np.int32),
                              dret)
@@ -745,7 +688,10 @@ def _full_size(gpu, host, lens, bs, cls):
     assert (dret.cpu().numpy() == lens).all()
     U = int(lens.sum())
     assert torch.equal(d_out[:U], d_src[:U])
-    del d_out, d_src
+    # guards: nothing written outside [dst_off, dst_off + dst_cap) on either side
+    gpu_batch.check_guards_strided(d_dst, image, slot, caps, "compress")
+    gpu_batch.check_guards_strided(d_out, image[:n * bs + 64], bs, lens, "decompress[auto]")
+    del d_out, d_src, image
     L = oracle_ref.load()
     c_out = np.zeros(n * slot, np.uint8)
     c_ret = np.zeros(n, np.int32)
@@ -969,7 +915,6 @@ def test_dict_decompress_forced_decoders(gpu, dec):
     Valid frames, truncations, flips and short capacities: values and bytes
     equal the oracle's restatement of the extDict branches
     (lz4e_decompress.c:299-302, 339-378)."""
-    import torch
     rng = np.random.default_rng(77 + dec)
     pool = _corpus("mixed", 1 << 20, 29).tobytes()
     frames, caps, dicts, want = [], [], [], []
@@ -998,40 +943,12 @@ def test_dict_decompress_forced_decoders(gpu, dec):
         caps.append(cap)
         dicts.append(dic)
         want.append(oracle_ref.decompress_dict(f, cap, dic))
-    # device layout: [dictionary | output capacity] per block, frames packed
-    dev = torch.device("cuda")
-    n = len(frames)
-    soffs = np.concatenate([[0], np.cumsum([(len(f) + 15) // 16 * 16 for f in frames])[:-1]]).astype(np.int64)
-    src = np.zeros(int(soffs[-1]) + len(frames[-1]) + 16, np.uint8)
-    for i, f in enumerate(frames):
-        src[soffs[i]:soffs[i] + len(f)] = np.frombuffer(f, np.uint8)
-    doffs, pos = [], 0
-    for i in range(n):
-        pos += (len(dicts[i]) + 15) // 16 * 16
-        doffs.append(pos)
-        pos += (max(caps[i], 1) + 79) // 16 * 16
-    out = np.zeros(pos + 64, np.uint8)
-    for i in range(n):
-        if dicts[i]:
-            out[doffs[i] - len(dicts[i]):doffs[i]] = np.frombuffer(dicts[i], np.uint8)
-    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt)).to(dev)
-    d_out = t(out, np.uint8)
-    ret = torch.full((n,), -7777, dtype=torch.int32, device=dev)
-    L = gpu.lib()
-    P = ctypes.c_void_p
-    L.lz4e_debug_decompress_dict.argtypes = [P] * 7 + [ctypes.c_uint32, ctypes.c_uint32, P, P, ctypes.c_uint32]
-    a = [t(src, np.uint8), t(soffs, np.int64), t([len(f) for f in frames], np.int32), t(doffs, np.int64),
-         t(caps, np.int32), t([len(d) for d in dicts], np.int32)]
-    assert L.lz4e_debug_decompress_dict(a[0].data_ptr(), a[1].data_ptr(), a[2].data_ptr(), d_out.data_ptr(),
-                                        a[3].data_ptr(), a[4].data_ptr(), ret.data_ptr(), n, max(caps),
-                                        a[5].data_ptr(), None, dec) == 0
-    torch.cuda.synchronize()
-    r = ret.cpu().numpy()
-    o = d_out.cpu().numpy()
+    # device layout: [dictionary | output capacity] per block, guards on
+    r, outs = gpu_batch.decompress(gpu, frames, caps, max_cap=max(caps), mode=dec, dicts=dicts)
     for i, (er, eb) in enumerate(want):
         assert r[i] == er, (i, r[i], er)
         if er >= 0:
-            assert o[doffs[i]:doffs[i] + er].tobytes() == eb, i
+            assert outs[i] == eb, i
 
 
 def test_dict_streams_device_resident(gpu):
@@ -1054,7 +971,8 @@ def test_dict_streams_device_resident(gpu):
     slot = (cap + 64 + 15) // 16 * 16
     doffs = np.arange(n, dtype=np.int64) * slot
     t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt)).to(dev)
-    dst = torch.zeros(n * slot, dtype=torch.uint8, device=dev)
+    image = gpu_batch.device_pattern(max(n * slot, n * bs + 64), dev)
+    dst = image[:n * slot].clone()
     ret = torch.zeros(n, dtype=torch.int32, device=dev)
     L = amd.lib()
     ptr = lambda x: x.data_ptr()
@@ -1064,6 +982,7 @@ def test_dict_streams_device_resident(gpu):
                                           ptr(d_doff), ptr(d_cap), ptr(ret), None, n, bs,
                                           ptr(d_dl), None) == 0
     torch.cuda.synchronize()
+    gpu_batch.check_guards_strided(dst, image[:n * slot], slot, [cap] * n, "compress_dict")
     r = ret.cpu().numpy()
     d = dst.cpu().numpy()
     for i in range(n):
@@ -1074,7 +993,7 @@ def test_dict_streams_device_resident(gpu):
         assert r[i] == er and d[doffs[i]:doffs[i] + r[i]].tobytes() == ef, i
     # decode: launch k decodes block k of every stream into the stream's
     # contiguous output, after block k-1 (its dictionary)
-    out = torch.zeros(n * bs + 64, dtype=torch.uint8, device=dev)
+    out = image[:n * bs + 64].clone()
     dret = torch.full((n,), -9, dtype=torch.int32, device=dev)
     for k in range(K):
         idx = np.array([s * K + k for s in range(S)])
@@ -1088,6 +1007,7 @@ def test_dict_streams_device_resident(gpu):
     torch.cuda.synchronize()
     assert (dret.cpu().numpy() == bs).all()
     assert np.array_equal(out[:n * bs].cpu().numpy(), host)
+    gpu_batch.check_guards_strided(out, image[:n * bs + 64], bs, [bs] * n, "decompress_dict")
 
 
 # ---------------------------------------------------------------------------

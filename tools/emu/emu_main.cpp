@@ -14,10 +14,57 @@
 // With DICT_FILE the block is compressed in dictionary mode against the
 // file's last <= 64 KiB (staged right before the block, as the library does).
 // Buffers are sized exactly (no slack) so that ASan sees any overrun.
+// A leading "--skew S,D" (0..15 each) places the input S bytes and the output
+// D bytes past a 16-byte boundary; the buffers still end exactly where the
+// block does (inputs at the end of the aligned dword holding their last byte,
+// which the kernels may read).
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include <vector>
+
+#if defined(__has_feature)
+#if __has_feature(address_sanitizer)
+#include <sanitizer/asan_interface.h>
+#define EMU_POISON(p, n) ASAN_POISON_MEMORY_REGION(p, n)
+#define EMU_UNPOISON(p, n) ASAN_UNPOISON_MEMORY_REGION(p, n)
+#endif
+#endif
+#ifndef EMU_POISON
+#define EMU_POISON(p, n) ((void)0)
+#define EMU_UNPOISON(p, n) ((void)0)
+#endif
+
+static unsigned g_src_skew = 0, g_dst_skew = 0;
+static bool g_skewed = false;  // without --skew the buffers start at the heap block's start
+
+// `size` bytes whose byte `lead` sits `skew` bytes past a 16-byte boundary.
+// The heap block ends at the region's end (input: rounded up to the aligned
+// dword); the pad in front holds a canary, and its whole 8-byte granules are
+// poisoned, so a store before the region is caught by ASan or by ok().
+struct Skewed {
+    uint8_t* base = nullptr;
+    uint8_t* p = nullptr;
+    size_t pad = 0;
+    Skewed(size_t size, size_t lead, unsigned skew, bool input) {
+        pad = g_skewed ? (size_t)((skew + 16 - lead % 16) % 16) : 0;
+        size_t total = pad + size;
+        if (input) total = (total + 3) & ~(size_t)3;
+        if (posix_memalign((void**)&base, 16, total ? total : 1)) exit(2);
+        memset(base, 0, total);
+        memset(base, 0xC7, pad);
+        EMU_POISON(base, pad & ~(size_t)7);
+        p = base + pad;
+    }
+    bool ok() const {
+        EMU_UNPOISON(base, pad & ~(size_t)7);
+        for (size_t i = 0; i < pad; ++i)
+            if (base[i] != 0xC7) return false;
+        return true;
+    }
+    ~Skewed() { free(base); }
+};
 
 extern "C" int emu_compress_batch(const uint8_t* src, const uint64_t* src_off, const uint32_t* src_len,
                                   const uint8_t* table_type, uint8_t* dst, const uint64_t* dst_off,
@@ -54,32 +101,44 @@ static int decode_main(int argc, char** argv) {
     std::vector<uint8_t> dict;
     if (argc > 5) dict = slurp(argv[5]);
     const int32_t D = (int32_t)(dict.size() > 65536 ? 65536 : dict.size());
-    std::vector<uint8_t> out(dict.end() - D, dict.end());
-    out.resize((size_t)D + (size_t)cap);
+    Skewed out((size_t)D + (size_t)cap, (size_t)D, g_dst_skew, false);
+    if (D) memcpy(out.p, dict.data() + dict.size() - D, (size_t)D);
     const int32_t csize = (int32_t)frame.size();
     const uint64_t so = 0, doff = (uint64_t)D;
     int32_t ret = -7777;
-    if (frame.empty()) frame.push_back(0);  // a valid pointer for csize 0
     // the decoder reads the input window by aligned dwords (the GPU's word
-    // granularity: the dword holding the last byte); the heap block covers it
-    frame.reserve((frame.size() + 3) & ~(size_t)3);
+    // granularity: the dwords holding the first and the last byte); the heap
+    // block covers them (at least one byte, a valid pointer for csize 0)
+    Skewed in(frame.empty() ? 1 : frame.size(), 0, g_src_skew, true);
+    if (!frame.empty()) memcpy(in.p, frame.data(), frame.size());
     // kDecPipe / kDecSmall / kDecGroup / kDecWave
     const char m = argv[1][1];
     const uint32_t mode = m == 'p' ? 2u : (m == 'l' ? 6u : (m == 'g' ? 7u : (m == 'G' ? 9u : 1u)));
-    emu_decompress_batch_mode(frame.data(), &so, &csize, out.data(), &doff, &cap, &ret, 1, &D, mode);
+    emu_decompress_batch_mode(in.p, &so, &csize, out.p, &doff, &cap, &ret, 1, &D, mode);
+    if (!out.ok() || !in.ok()) {
+        fprintf(stderr, "emu_main: a store in front of a buffer\n");
+        return 3;
+    }
     char err[256];
     const int good = emu_decode_results(&ret, 1, err, sizeof err);
     printf("ret %d\nresults %d %s\n", ret, good, err);
     if (argc > 4 && ret > 0) {
         FILE* o = fopen(argv[4], "wb");
         if (!o) return 2;
-        fwrite(out.data() + D, 1, (size_t)ret, o);
+        fwrite(out.p + D, 1, (size_t)ret, o);
         fclose(o);
     }
     return 0;
 }
 
 int main(int argc, char** argv) {
+    if (argc > 2 && !strcmp(argv[1], "--skew")) {
+        if (sscanf(argv[2], "%u,%u", &g_src_skew, &g_dst_skew) != 2 || g_src_skew > 15 || g_dst_skew > 15) return 2;
+        g_skewed = true;
+        argv[2] = argv[0];
+        argv += 2;
+        argc -= 2;
+    }
     if (argc > 3 && argv[1][0] == '-' &&
         (argv[1][1] == 'd' || argv[1][1] == 'p' || argv[1][1] == 'l' || argv[1][1] == 'g' || argv[1][1] == 'G'))
         return decode_main(argc, argv);
@@ -99,20 +158,25 @@ int main(int argc, char** argv) {
     std::vector<uint8_t> dict;
     if (argc > 4) dict = slurp(argv[4]);
     uint32_t D = (uint32_t)dict.size() > 65536 ? 65536 : (uint32_t)dict.size();
-    std::vector<uint8_t> src(dict.end() - D, dict.end()), dst(cap);
-    src.insert(src.end(), in.begin(), in.end());
+    Skewed src((size_t)D + n, (size_t)D, g_src_skew, true), dst(cap, 0, g_dst_skew, false);
+    if (D) memcpy(src.p, dict.data() + dict.size() - D, (size_t)D);
+    if (n) memcpy(src.p + D, in.data(), n);
     const uint64_t so = D, doff = 0;
     int32_t ret = -7;
     uint32_t aux[2] = {0, 0};
     if (argc > 4)
-        emu_compress_batch_dict(src.data(), &so, &n, &tt, dst.data(), &doff, &cap, &ret, aux, 1, n, &D);
+        emu_compress_batch_dict(src.p, &so, &n, &tt, dst.p, &doff, &cap, &ret, aux, 1, n, &D);
     else
-        emu_compress_batch(src.data(), &so, &n, &tt, dst.data(), &doff, &cap, &ret, aux, 1, n);
+        emu_compress_batch(src.p, &so, &n, &tt, dst.p, &doff, &cap, &ret, aux, 1, n);
+    if (!dst.ok() || !src.ok()) {
+        fprintf(stderr, "emu_main: a store in front of a buffer\n");
+        return 3;
+    }
     printf("ret %d aux %u %u\n", ret, aux[0], aux[1]);
     if (argc > 3 && ret > 0) {
         FILE* o = fopen(argv[3], "wb");
         if (!o) return 2;
-        fwrite(dst.data(), 1, (size_t)ret, o);
+        fwrite(dst.p, 1, (size_t)ret, o);
         fclose(o);
     }
     return 0;
