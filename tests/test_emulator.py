@@ -529,3 +529,159 @@ def test_emulated_decoders_on_synthesized_frames(emu_exe, tmp_path, profile):
             assert got[0] == want[0], (c.label, flag, skew, got[0], want[0])
             if want[0] >= 0:
                 assert got[1] == want[1], (c.label, flag, skew)
+
+
+# ---------------------------------------------------------------------------
+# Planted inputs (tests/parse_synth.py): every named match length, literal
+# run, catch-up, offset, block end and clash group through compress_block's
+# source under ASan + UBSan; frame, value and iterator post-state equal the
+# oracle's.  emu_main --cap N gives the kernel an output buffer of exactly N
+# bytes, so a store outside a limited output is caught.  The processes run a
+# few at a time (each is 64 lane threads that mostly wait for each other).
+# ---------------------------------------------------------------------------
+
+import parse_synth  # noqa: E402
+from concurrent.futures import ThreadPoolExecutor  # noqa: E402
+
+_JOBS = max(1, min(8, os.cpu_count() or 1))
+
+
+def _planted_run(exe, tmp_path, key, c, cap=None, skew=None):
+    """One planted case through emu_main against the oracle -> None or what differs."""
+    blk, frame, dct = tmp_path / f"b{key}.bin", tmp_path / f"f{key}.bin", tmp_path / f"d{key}.bin"
+    blk.write_bytes(c.block)
+    args = [exe]
+    if skew is not None:
+        args += ["--skew", "%d,%d" % skew]
+    if cap is not None:
+        args += ["--cap", str(cap)]
+    args += [str(blk), str(c.tt), str(frame)]
+    if c.dic:
+        dct.write_bytes(c.dic)
+        args.append(str(dct))
+    out = subprocess.run(args, capture_output=True, text=True, timeout=1200)
+    if out.returncode != 0 or "ERROR: AddressSanitizer" in out.stderr or "runtime error" in out.stderr:
+        return (c.label, c.tt, cap, skew, out.returncode, out.stderr[-1500:])
+    _, r, _, fs, lr = out.stdout.split()
+    if c.dic:
+        er, ef = oracle_ref.compress_dict(c.block, c.dic, cap)
+        eaux = None
+    else:
+        er, ef, efs, elr = oracle_ref.compress(c.block, c.tt, cap)
+        eaux = (efs, elr)
+    if int(r) != er:
+        return (c.label, c.tt, cap, skew, "value", int(r), er)
+    if er > 0:
+        if frame.read_bytes() != ef:
+            return (c.label, c.tt, cap, skew, "frame")
+        if eaux is not None and (int(fs), int(lr)) != eaux:
+            return (c.label, c.tt, cap, skew, "post-state", (int(fs), int(lr)), eaux)
+    elif frame.exists():
+        return (c.label, c.tt, cap, skew, "a refused block wrote a frame file")
+    return None
+
+
+def _planted_all(exe, tmp_path, runs):
+    """runs: [(case, cap, skew)] -> asserts that none differs."""
+    with ThreadPoolExecutor(_JOBS) as ex:
+        bad = [b for b in ex.map(lambda kr: _planted_run(exe, tmp_path, kr[0], *kr[1]), enumerate(runs)) if b]
+    assert not bad, bad[:5]
+
+
+def _family_cases(family):
+    if family == "dict":
+        return list(parse_synth.cases("dict", BYU32))
+    return [c for tt in parse_synth.CLASSES for c in parse_synth.cases(family, tt)]
+
+
+def _one_per_family(family):
+    """The two cases of a family that also run skewed and one byte under the
+    bound: its first byU16 case and its last byU32 case (dict: first and last)."""
+    cs = _family_cases(family)
+    u16 = [c for c in cs if c.tt == BYU16] or cs
+    u32 = [c for c in cs if c.tt == BYU32]
+    return [u16[0], u32[-1]]
+
+
+@pytest.mark.parametrize("family", parse_synth.FAMILIES)
+def test_emulated_planted_family(emu_exe, tmp_path, family):
+    """Every case of the family in every table class it is built for; two of
+    them also at a skewed placement and with the output one byte under the
+    bound (limited output: the exact walk instead of the fast chain)."""
+    runs = [(c, None, None) for c in _family_cases(family)]
+    for k, c in enumerate(_one_per_family(family)):
+        runs.append((c, None, ((3 + 7 * k) % 16, (5 * k + 3) % 16)))
+        runs.append((c, parse_synth.bound(len(c.block)) - 1, None))
+    _planted_all(emu_exe, tmp_path, runs)
+
+
+def _sweep_caps(c, count=40):
+    """About `count` capacities spread over 0 .. the bound, the frame's size
+    and its neighbours among them."""
+    full = oracle_ref.compress(c.block, c.tt)[0]
+    b = parse_synth.bound(len(c.block))
+    caps = {int(x) for x in np.linspace(0, b, count - 4)} | {full - 1, full, full + 1, b - 1}
+    return sorted(caps)
+
+
+def test_emulated_planted_capacity_sweep(emu_exe, tmp_path):
+    """The three capacity-sweep blocks at about 40 capacities each from 0 to
+    the bound, in an output buffer of exactly that size: the refusals are the
+    oracle's, an accepted frame is the oracle's, and no store leaves the
+    buffer (ASan, the canary in front of it)."""
+    runs = [(c, cap, None) for c in parse_synth.capacity_sweep() for cap in _sweep_caps(c)]
+    assert len(runs) >= 3 * 38
+    _planted_all(emu_exe, tmp_path, runs)
+
+
+UNREACHED = os.path.join(REPO, "tests", "golden", "compress_unreached.txt")
+
+
+def test_compress_block_unreached_lines(tmp_path):
+    """Line coverage of compress_block over the planted cases (gcov on a
+    --coverage build of the emulator, tools/emu/coverage.sh): every line that
+    no case executes is listed, with its reason, in
+    tests/golden/compress_unreached.txt."""
+    if shutil.which("gcov") is None:
+        pytest.skip("no gcov")
+    if not os.path.exists(CXX):
+        pytest.skip("no clang++ for the emulator")
+    lines = []
+    k = 0
+
+    def add(c, cap=None):
+        nonlocal k
+        blk, dct = tmp_path / f"b{k}.bin", tmp_path / f"d{k}.bin"
+        k += 1
+        blk.write_bytes(c.block)
+        a = (["--cap", str(cap)] if cap is not None else []) + [str(blk), str(c.tt)]
+        if c.dic:
+            dct.write_bytes(c.dic)
+            a += ["/dev/null", str(dct)]
+        lines.append(" ".join(a))
+
+    for family in parse_synth.FAMILIES:
+        for c in _family_cases(family):
+            add(c)
+        for c in _one_per_family(family):
+            add(c, parse_synth.bound(len(c.block)) - 1)
+    for c in parse_synth.capacity_sweep():
+        for cap in _sweep_caps(c):
+            add(c, cap)
+    manifest = tmp_path / "manifest.txt"
+    manifest.write_text("\n".join(lines) + "\n")
+    env = dict(os.environ, CXX=CXX, TMPDIR=str(tmp_path))
+    out = subprocess.run(["bash", os.path.join(REPO, "tools", "emu", "coverage.sh"), str(manifest), str(_JOBS)],
+                         capture_output=True, text=True, timeout=3000, env=env)
+    assert out.returncode == 0, out.stderr[-2000:]
+    missed = [ln for ln in out.stdout.split("\n") if ln.strip()]
+    allowed = set()
+    for ln in open(UNREACHED):
+        if ln.startswith("#") or not ln.strip():
+            continue
+        text, _, reason = ln.rstrip("\n").partition("\t# ")
+        assert reason.strip(), f"no reason for {text!r}"
+        allowed.add(text.strip())
+    assert len(missed) < 200, "gcov saw no run at all"
+    extra = [ln for ln in missed if ln not in allowed]
+    assert not extra, extra

@@ -18,6 +18,10 @@
 // D bytes past a 16-byte boundary; the buffers still end exactly where the
 // block does (inputs at the end of the aligned dword holding their last byte,
 // which the kernels may read).
+// A leading "--cap N" makes the compressor's output buffer exactly N bytes
+// (default: the block's bound, n + n/255 + 16), so ASan and the canary see any
+// store outside a limited output; a block that is refused (ret 0) writes no
+// FRAME_OUT.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -49,6 +53,7 @@ struct Skewed {
     size_t pad = 0;
     Skewed(size_t size, size_t lead, unsigned skew, bool input) {
         pad = g_skewed ? (size_t)((skew + 16 - lead % 16) % 16) : 0;
+        if (!input && pad + size == 0) pad = 16;  // an empty output buffer: every store is in front of it
         size_t total = pad + size;
         if (input) total = (total + 3) & ~(size_t)3;
         if (posix_memalign((void**)&base, 16, total ? total : 1)) exit(2);
@@ -132,9 +137,17 @@ static int decode_main(int argc, char** argv) {
 }
 
 int main(int argc, char** argv) {
-    if (argc > 2 && !strcmp(argv[1], "--skew")) {
-        if (sscanf(argv[2], "%u,%u", &g_src_skew, &g_dst_skew) != 2 || g_src_skew > 15 || g_dst_skew > 15) return 2;
-        g_skewed = true;
+    long cap_arg = -1;
+    while (argc > 2 && (!strcmp(argv[1], "--skew") || !strcmp(argv[1], "--cap"))) {
+        if (!strcmp(argv[1], "--cap")) {
+            char* end = nullptr;
+            cap_arg = strtol(argv[2], &end, 10);
+            if (!*argv[2] || *end || cap_arg < 0 || cap_arg > 0x7FFFFFFFL) return 2;
+        } else {
+            if (sscanf(argv[2], "%u,%u", &g_src_skew, &g_dst_skew) != 2 || g_src_skew > 15 || g_dst_skew > 15)
+                return 2;
+            g_skewed = true;
+        }
         argv[2] = argv[0];
         argv += 2;
         argc -= 2;
@@ -143,7 +156,7 @@ int main(int argc, char** argv) {
         (argv[1][1] == 'd' || argv[1][1] == 'p' || argv[1][1] == 'l' || argv[1][1] == 'g' || argv[1][1] == 'G'))
         return decode_main(argc, argv);
     if (argc < 3) {
-        fprintf(stderr, "usage: emu_main BLOCK_FILE TABLE_CLASS [FRAME_OUT]\n");
+        fprintf(stderr, "usage: emu_main [--skew S,D] [--cap N] BLOCK_FILE TABLE_CLASS [FRAME_OUT [DICT_FILE]]\n");
         return 2;
     }
     FILE* f = fopen(argv[1], "rb");
@@ -154,7 +167,7 @@ int main(int argc, char** argv) {
     fclose(f);
     const uint32_t n = (uint32_t)in.size();
     const uint8_t tt = (uint8_t)atoi(argv[2]);
-    const uint32_t cap = n + n / 255 + 16;
+    const uint32_t cap = cap_arg >= 0 ? (uint32_t)cap_arg : n + n / 255 + 16;
     std::vector<uint8_t> dict;
     if (argc > 4) dict = slurp(argv[4]);
     uint32_t D = (uint32_t)dict.size() > 65536 ? 65536 : (uint32_t)dict.size();
