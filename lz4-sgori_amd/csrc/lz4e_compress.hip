@@ -31,6 +31,9 @@
 //    those lane groups are resolved with one ballot per group.  The first
 //    verifying lane is the reference's match; the table is then fixed up to
 //    hold exactly the puts of the probes up to it.
+//  * A block read from HBM whose output cannot fill up does not emit from
+//    inside the parse at all: its sequences become 8-byte records, written
+//    out as frame bytes 64 at a time (deferred emit, flush_records).
 //
 // Stores may write up to 3 bytes past the bytes they own when a later store
 // of the same wave (program order) rewrites those bytes, and never past the
@@ -40,6 +43,8 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
+
+#include <mutex>
 
 #include "lz4e_device.h"
 #include "lz4e_gpu.h"
@@ -285,6 +290,143 @@ LZ4E_DEV uint32_t back_from(const IMG& img, uint32_t p, uint32_t c, uint32_t roo
     return room;
 }
 
+// ---- deferred emit ---------------------------------------------------------
+// A block whose output cannot fill up (capacity >= its bound) does not write
+// its frame from inside the parse: the parse never reads what it emitted, so
+// each sequence only leaves an 8-byte record (one predicated store, no
+// cross-lane step on the per-window chain), and flush_records turns the
+// records into frame bytes 64 at a time -- when fewer than 64 record slots are
+// free, and at the block's end.  The records of block b are slots
+// [b * R, (b + 1) * R) of the launch's record buffer.
+//
+// Record: offset (16 bits), literal length and match length (24 bits each,
+// blocks of >= 2^24 bytes emit inline), the low bytes of the lengths in the
+// first dword -- the fast chain's `fe` is a record as it stands.  Match length
+// 0: the last literals.
+typedef __attribute__((address_space(1))) uint64_t gu64;
+constexpr uint32_t kRecLenBits = 24;
+constexpr uint32_t kShortLit = 32;  // literal runs up to here are copied by their record's lane
+
+LZ4E_DEV uint64_t make_record(uint32_t off, uint32_t L, uint32_t ml) {
+    return (uint64_t)(off | ((L & 0xFFu) << 16) | ((ml & 0xFFu) << 24)) |
+           ((uint64_t)((L >> 8) | ((ml >> 8) << 16)) << 32);
+}
+
+// One sequence found by the exact walk, a search or at the block's end.
+LZ4E_DEV void record_seq(gu64* rec, uint32_t& nrec, uint32_t off, uint32_t L, uint32_t ml,
+                         uint32_t lane) {
+    if (lane == 0) rec[nrec] = make_record(off, L, ml);
+    nrec += 1;
+}
+
+// Frame bytes of the nrec recorded sequences, in order (lz4e_compress.c:352-453,
+// :500-530): op is the frame position and rpos the input position the first of
+// them starts at; both move past them and nrec returns to 0.  Lane q of a step
+// sizes record q, two prefix sums place every sequence in the frame and in the
+// input, and each lane writes its own token, one-byte extensions, offset and
+// (up to kShortLit) literals, exactly those bytes (whole dwords, then bytes).  Longer literal runs and
+// longer extensions go first, wave-wide and in order: a copy's spare bytes are
+// then rewritten by the bytes that belong there.
+template <bool kStamps, class IMG>
+LZ4E_DEV void flush_records(const IMG& img, gu8* out, const gu64* rec, uint32_t& nrec, uint32_t& op,
+                            uint32_t& rpos, Stamps& st, uint32_t lane) {
+    wave_fence();  // the record stores, then the loads of other lanes' records
+    for (uint32_t base = 0; base < nrec; base += kWave) {
+        const bool act = base + lane < nrec;
+        const uint64_t r = act ? rec[base + lane] : 0;
+        const uint32_t w0 = (uint32_t)r, w1 = (uint32_t)(r >> 32);
+        const uint32_t off = w0 & 0xFFFFu;
+        const uint32_t L = ((w0 >> 16) & 0xFFu) | ((w1 & 0xFFFFu) << 8);
+        const uint32_t ml = (w0 >> 24) | ((w1 >> 16) << 8);
+        const uint32_t mc = ml - 4;  // (ml == 0: no match part)
+        const uint32_t lx = L >= 15 ? (L - 15) / 255 + 1 : 0;
+        const uint32_t mx = ml == 0 ? 0 : 2 + (mc >= 15 ? (mc - 15) / 255 + 1 : 0);
+        const uint32_t size = act ? 1 + lx + L + mx : 0;
+        const uint32_t span = act ? L + ml : 0;
+        const uint32_t oe = wave_incl_add(size), pe = wave_incl_add(span);
+        const uint32_t o = op + oe - size;      // token
+        const uint32_t lo = o + 1 + lx;         // literals
+        const uint32_t ip = rpos + pe - span;   // their source
+        uint64_t wide = ballot(act && (L > kShortLit || lx > 1 || mx > 3));
+        while (wide) {
+            const uint32_t q = ctz64(wide);
+            wide &= wide - 1;
+            const uint32_t Lq = lane_val(L, q), mlq = lane_val(ml, q), loq = lane_val(lo, q);
+            if (Lq >= 15 + 255) out_ext(out, lane_val(o, q) + 1, Lq - 15, lane);
+            if (Lq > kShortLit) {
+                if (mlq != 0) out_copy(out, loq, img, lane_val(ip, q), Lq, lane);
+                else out_copy_exact(out, loq, img, lane_val(ip, q), Lq, lane);
+            }
+            lockstep();  // the extension overwrites the copy's spare bytes
+            if (mlq >= 4 + 15 + 255) out_ext(out, loq + Lq + 2, mlq - 4 - 15, lane);
+        }
+        lockstep();  // so do the tokens and offsets below
+        const uint32_t Ls = act && L <= kShortLit ? L : 0, whole = Ls & ~3u;
+        uint32_t tail[3], w[kShortLit / 4];  // every load first: one round trip for the step
+#pragma unroll
+        for (uint32_t j = 0; j < 3; ++j) tail[j] = whole + j < Ls ? img.rd8(ip + whole + j) : 0;
+#pragma unroll
+        for (uint32_t j = 0; j < kShortLit / 4; ++j) w[j] = 4 * j < whole ? img.ld32(ip + 4 * j) : 0;
+#pragma unroll
+        for (uint32_t j = 0; j < kShortLit / 4; ++j)
+            if (4 * j < whole) st32(out, lo + 4 * j, w[j]);
+#pragma unroll
+        for (uint32_t j = 0; j < 3; ++j)
+            if (whole + j < Ls) out[lo + whole + j] = (uint8_t)tail[j];
+        if (act) {
+            out[o] = (uint8_t)(((L < 15 ? L : 15) << 4) | (ml == 0 ? 0 : (mc < 15 ? mc : 15)));
+            if (lx == 1) out[o + 1] = (uint8_t)(L - 15);
+            if (ml != 0) {
+                out[lo + L] = (uint8_t)off;
+                out[lo + L + 1] = (uint8_t)(off >> 8);
+                if (mx == 3) out[lo + L + 2] = (uint8_t)(mc - 15);
+            }
+        }
+        op += lane_val(oe, kWave - 1);
+        rpos += lane_val(pe, kWave - 1);
+    }
+    nrec = 0;
+    if (kStamps) st.lap(kPhTail);
+}
+
+// The sequences of a fast chain (compress_block): event lane l holds sequence
+// fe -- offset | literal length << 16 | match length << 24 -- of the chain's
+// events evm, nev of them; window lane x holds literal byte B + x in d0.
+// Deferred: every event lane stores its record.  Inline: lane q writes
+// sequence q's token, extension bytes and offset, window lane x its literal
+// byte (lz4e_compress.c:352-453).
+template <bool kDefer>
+LZ4E_DEV void chain_out(gu8* out, uint32_t& op, gu64* rec, uint32_t& nrec, uint64_t evm, uint32_t nev,
+                        uint32_t fe, uint32_t d0, uint64_t lanes_below, uint32_t lane) {
+    const bool isev = (evm >> lane) & 1;
+    if constexpr (kDefer) {
+        if (isev) rec[nrec + popc64(evm & lanes_below)] = fe;
+        nrec += nev;
+    } else {
+        // ev: lane q < nev holds the lane of event q
+        const uint32_t ev = push_lane(lane, isev ? popc64(evm & lanes_below) : 63);
+        const uint32_t f = shfl(fe, lane < nev ? ev : 0);
+        const uint32_t L = (f >> 16) & 0xFF, mc = (f >> 24) - 4;
+        const uint32_t hdr = L >= 15 ? 2 : 1;
+        const uint32_t size = lane < nev ? hdr + L + 2 + (mc >= 15 ? 1 : 0) : 0;
+        const uint32_t o = op + wave_incl_add(size) - size;
+        if (lane < nev) {
+            out[o] = (uint8_t)(((L < 15 ? L : 15) << 4) | (mc < 15 ? mc : 15));
+            if (L >= 15) out[o + 1] = (uint8_t)(L - 15);
+            out[o + hdr + L] = (uint8_t)f;
+            out[o + hdr + L + 1] = (uint8_t)(f >> 8);
+            if (mc >= 15) out[o + hdr + L + 2] = (uint8_t)(mc - 15);
+        }
+        // literal byte of lane x: run of the last event lane s <= x
+        const uint64_t le = evm & (lane >= 63 ? ~0ull : ((2ull << lane) - 1));
+        const uint32_t s = le ? 63 - (uint32_t)__builtin_clzll(le) : 0;
+        const uint32_t qi = popc64(evm & ((1ull << s) - 1));
+        const uint32_t Lq = shfl(L, qi), dq = shfl(o + hdr, qi);
+        if (le && lane - s < Lq) out[dq + lane - s] = (uint8_t)d0;
+        op = lane_val(o + size, nev - 1);
+    }
+}
+
 constexpr uint32_t kFwdW = 8;            // dwords of forward bytes held per position
 constexpr uint32_t kFwd = 4 * kFwdW;      // 32 bytes: matches shorter than this stay in registers
 constexpr uint32_t kLong = 1u << 31;  // ml flag: kFwd bytes equal, the count goes on
@@ -398,9 +540,12 @@ struct CResult {
 #endif
 constexpr uint32_t kGenericFrom = LZ4E_GENERIC_FROM;
 
-template <int TT, bool kStamps, class IMG>
+// kDefer (the kernel picks it per block): the output is unlimited and the
+// sequences go to the block's records rec[0 .. rlim + 64) (deferred emit).
+template <int TT, bool kStamps, bool kDefer, class IMG>
 LZ4E_DEV CResult compress_block(const IMG& img, uint32_t* smem, uint32_t n, gu8* out, uint32_t cap,
-                                uint64_t* dbg, uint32_t lane, uint32_t D = 0, bool progress_prio = true) {
+                                uint64_t* dbg, uint32_t lane, uint32_t D, bool progress_prio, gu64* rec,
+                                uint32_t rlim) {
     CResult res;
     // Dictionary mode (D > 0): the image is [D dictionary bytes | the n-byte
     // block], the parse starts at D and the table was preloaded from the
@@ -410,8 +555,9 @@ LZ4E_DEV CResult compress_block(const IMG& img, uint32_t* smem, uint32_t n, gu8*
     // limited output (lz4e_compress.c:553-560): the output checks compare
     // against capl, which is the capacity when limited and never reached
     // otherwise (one SGPR instead of a flag and the capacity)
-    const uint32_t capl = cap < bound ? cap : 0xFFFFFFFFu;
+    const uint32_t capl = (kDefer || cap >= bound) ? 0xFFFFFFFFu : cap;
     uint32_t op = 0, anchor = D, ip = D;
+    uint32_t nrec = 0, rpos = D;  // deferred emit: records waiting, the input position of the first
     [[maybe_unused]] uint32_t trn = 0;
     Stamps st;
     if (kStamps) st.start();
@@ -487,6 +633,7 @@ LZ4E_DEV CResult compress_block(const IMG& img, uint32_t* smem, uint32_t n, gu8*
         };
         for (;;) {
             // ================= window setup =================================
+            if constexpr (kDefer) if (nrec > rlim) flush_records<kStamps>(img, out, rec, nrec, op, rpos, st, lane);
             if (e >= prio_next) {
                 const uint32_t q = (uint32_t)(((uint64_t)(e - D) * 4) / n);
                 prio_next = q >= 4 ? ~0u : D + (uint32_t)(((uint64_t)(q + 1) * n + 3) / 4);
@@ -652,7 +799,7 @@ LZ4E_DEV CResult compress_block(const IMG& img, uint32_t* smem, uint32_t n, gu8*
                     // candidate only depends on puts before it).
                     if (kStamps) st.lap(kPhStripe);
                     const uint32_t ks = e - B;
-                    uint32_t k = ks, nev = 0, ev = 0;
+                    uint32_t k = ks, nev = 0;
                     uint64_t evm = 0, pch = 0;
                     uint32_t fc = kStop, fe = 0, jv = lane;
                     if (ks < 64) {
@@ -745,34 +892,10 @@ LZ4E_DEV CResult compress_block(const IMG& img, uint32_t* smem, uint32_t n, gu8*
                             Pg = Pn | (k >= 64 ? 0 : lane_range(k, 63));
                         }
                         put |= pch;
-                        // ev: lane q < nev holds the lane of event q
-                        const bool isev = (evm >> lane) & 1;
-                        ev = push_lane(lane, isev ? popc64(evm & lanes_below) : 63);
                     }
                     if (kStamps) st.lap(kPhLit);
-                    if (nev) {
-                        // emit the nev sequences at once (lz4e_compress.c:352-453):
-                        // lane q writes sequence q's token, extension bytes and
-                        // offset; window lane x writes literal byte B + x.
-                        const uint32_t f = shfl(fe, lane < nev ? ev : 0);
-                        const uint32_t L = (f >> 16) & 0xFF, mc = (f >> 24) - 4;
-                        const uint32_t hdr = L >= 15 ? 2 : 1;
-                        const uint32_t size = lane < nev ? hdr + L + 2 + (mc >= 15 ? 1 : 0) : 0;
-                        const uint32_t o = op + wave_incl_add(size) - size;
-                        if (lane < nev) {
-                            out[o] = (uint8_t)(((L < 15 ? L : 15) << 4) | (mc < 15 ? mc : 15));
-                            if (L >= 15) out[o + 1] = (uint8_t)(L - 15);
-                            out[o + hdr + L] = (uint8_t)f;
-                            out[o + hdr + L + 1] = (uint8_t)(f >> 8);
-                            if (mc >= 15) out[o + hdr + L + 2] = (uint8_t)(mc - 15);
-                        }
-                        // literal byte of lane x: run of the last event lane s <= x
-                        const uint64_t le = evm & (lane >= 63 ? ~0ull : ((2ull << lane) - 1));
-                        const uint32_t s = le ? 63 - (uint32_t)__builtin_clzll(le) : 0;
-                        const uint32_t qi = popc64(evm & ((1ull << s) - 1));
-                        const uint32_t Lq = shfl(L, qi), dq = shfl(o + hdr, qi);
-                        if (le && lane - s < Lq) out[dq + lane - s] = (uint8_t)d0;
-                        op = lane_val(o + size, nev - 1);
+                    if (nev) {  // the chain's nev sequences, recorded or emitted at once
+                        chain_out<kDefer>(out, op, rec, nrec, evm, nev, fe, d0, lanes_below, lane);
                         e = B + k;
                         anchor = e;
                         if (kStamps) { st.cnt[1] += nev; st.cnt[3] += nev << 16; st.lap(kPhTail); }
@@ -816,8 +939,8 @@ LZ4E_DEV CResult compress_block(const IMG& img, uint32_t* smem, uint32_t n, gu8*
                     uint32_t t = m & ~kLong;
                     if (m & kLong) t = count_from(img, e, c, kFwd, matchlimit, lane);
                     LZ4E_TR(2, e, ((uint64_t)c << 32) | t);
-                    const uint32_t tok = op++;
-                    if (!emit_match(tok, 0, e - c, t - 4)) goto fail;
+                    if constexpr (kDefer) record_seq(rec, nrec, e - c, 0, t, lane);
+                    else if (!emit_match(op++, 0, e - c, t - 4)) goto fail;
                     if (kStamps) st.cnt[1]++;
                     e += t;
                     anchor = e;
@@ -909,25 +1032,29 @@ LZ4E_DEV CResult compress_block(const IMG& img, uint32_t* smem, uint32_t n, gu8*
                 LZ4E_TR(2, ipm, ((uint64_t)cand << 32) | t);
                 // literals [anchor, ipm) (lz4e_compress.c:352-382)
                 const uint32_t L = ipm - anchor;
-                const uint32_t tok = op++;
-                if ((uint64_t)op + L + 8 + L / 255 > capl) goto fail;
-                uint32_t tokhi;
-                if (L >= 15) {
-                    tokhi = 0xF0;
-                    op += out_ext(out, op, L - 15, lane);
+                if constexpr (kDefer) {
+                    record_seq(rec, nrec, ipm - cand, L, t, lane);
                 } else {
-                    tokhi = L << 4;
+                    const uint32_t tok = op++;
+                    if ((uint64_t)op + L + 8 + L / 255 > capl) goto fail;
+                    uint32_t tokhi;
+                    if (L >= 15) {
+                        tokhi = 0xF0;
+                        op += out_ext(out, op, L - 15, lane);
+                    } else {
+                        tokhi = L << 4;
+                    }
+                    if (anchor >= B) {
+                        // the run lies in the window: lane a0 + 4i stores bytes 4i..4i+3
+                        const uint32_t r = lane - (anchor - B);
+                        if ((r & 3) == 0 && r < L) st32(out, op + r, d0);
+                    } else {
+                        out_copy(out, op, img, anchor, L, lane);
+                    }
+                    op += L;
+                    lockstep();  // the offset overwrites the copy's spare bytes
+                    if (!emit_match(tok, tokhi, ipm - cand, t - 4)) goto fail;
                 }
-                if (anchor >= B) {
-                    // the run lies in the window: lane a0 + 4i stores bytes 4i..4i+3
-                    const uint32_t r = lane - (anchor - B);
-                    if ((r & 3) == 0 && r < L) st32(out, op + r, d0);
-                } else {
-                    out_copy(out, op, img, anchor, L, lane);
-                }
-                op += L;
-                lockstep();  // the offset overwrites the copy's spare bytes
-                if (!emit_match(tok, tokhi, ipm - cand, t - 4)) goto fail;
                 if (kStamps) { st.cnt[1]++; st.lap(kPhTail); }
                 e = ipm + t;
                 anchor = e;
@@ -1046,19 +1173,23 @@ LZ4E_DEV CResult compress_block(const IMG& img, uint32_t* smem, uint32_t n, gu8*
                 const uint32_t t = count_from(img, qh, ch, 4, matchlimit, lane) + cu;
                 LZ4E_TR(2, ipm, ((uint64_t)cand << 32) | t);
                 const uint32_t L = ipm - anchor;
-                const uint32_t tok = op++;
-                if ((uint64_t)op + L + 8 + L / 255 > capl) goto fail;
-                uint32_t tokhi;
-                if (L >= 15) {
-                    tokhi = 0xF0;
-                    op += out_ext(out, op, L - 15, lane);
+                if constexpr (kDefer) {
+                    record_seq(rec, nrec, ipm - cand, L, t, lane);
                 } else {
-                    tokhi = L << 4;
-                }
-                out_copy(out, op, img, anchor, L, lane);
-                op += L;
-                lockstep();
-                if (!emit_match(tok, tokhi, ipm - cand, t - 4)) goto fail;
+                    const uint32_t tok = op++;
+                    if ((uint64_t)op + L + 8 + L / 255 > capl) goto fail;
+                    uint32_t tokhi;
+                    if (L >= 15) {
+                        tokhi = 0xF0;
+                        op += out_ext(out, op, L - 15, lane);
+                    } else {
+                        tokhi = L << 4;
+                    }
+                    out_copy(out, op, img, anchor, L, lane);
+                    op += L;
+                    lockstep();
+                    if (!emit_match(tok, tokhi, ipm - cand, t - 4)) goto fail;
+                }  // inline emit
                 if (kStamps) { st.cnt[1]++; st.lap(kPhLit); }
                 e = ipm + t;
                 anchor = e;
@@ -1074,17 +1205,23 @@ LZ4E_DEV CResult compress_block(const IMG& img, uint32_t* smem, uint32_t n, gu8*
 last_literals: {
         // lz4e_compress.c:500-530
         const uint32_t R = D + n - anchor;
-        if ((uint64_t)op + R + 1 + (R + 240) / 255 > capl) goto fail;
-        if (R >= 15) {
-            if (lane == 0) out[op] = 0xF0;
-            op += 1;
-            op += out_ext(out, op, R - 15, lane);
+        if constexpr (kDefer) {
+            record_seq(rec, nrec, 0, R, 0, lane);
+            flush_records<kStamps>(img, out, rec, nrec, op, rpos, st, lane);
         } else {
-            if (lane == 0) out[op] = (uint8_t)(R << 4);
-            op += 1;
-        }
-        out_copy_exact(out, op, img, anchor, R, lane);
-        res.ret = (int32_t)(op + R);
+            if ((uint64_t)op + R + 1 + (R + 240) / 255 > capl) goto fail;
+            if (R >= 15) {
+                if (lane == 0) out[op] = 0xF0;
+                op += 1;
+                op += out_ext(out, op, R - 15, lane);
+            } else {
+                if (lane == 0) out[op] = (uint8_t)(R << 4);
+                op += 1;
+            }
+            out_copy_exact(out, op, img, anchor, R, lane);
+            op += R;
+        }  // inline emit
+        res.ret = (int32_t)op;
         res.a0 = ip - D;
         res.a1 = R;
         if (kStamps) {
@@ -1133,13 +1270,30 @@ LZ4E_DEV void stage_block(uint32_t* dstw, const uint8_t* src, uint32_t n, uint32
     }
 }
 
-template <bool kStamps, class IMG>
+template <bool kStamps, bool kDefer, class IMG>
 LZ4E_DEV CResult dispatch_class(const IMG& img, uint32_t* smem, uint32_t n, int tt, gu8* out,
-                                uint32_t cap, uint64_t* dbg, uint32_t lane, uint32_t D = 0,
-                                bool pp = true) {
-    if (tt == kByU32) return compress_block<kByU32, kStamps>(img, smem, n, out, cap, dbg, lane, D, pp);
-    if (tt == kByU16) return compress_block<kByU16, kStamps>(img, smem, n, out, cap, dbg, lane, 0, pp);
-    return compress_block<kByU64, kStamps>(img, smem, n, out, cap, dbg, lane, 0, pp);
+                                uint32_t cap, uint64_t* dbg, uint32_t lane, uint32_t D, bool pp,
+                                gu64* rec, uint32_t rlim) {
+    if (tt == kByU32)
+        return compress_block<kByU32, kStamps, kDefer>(img, smem, n, out, cap, dbg, lane, D, pp, rec, rlim);
+    if (tt == kByU16)
+        return compress_block<kByU16, kStamps, kDefer>(img, smem, n, out, cap, dbg, lane, 0, pp, rec, rlim);
+    return compress_block<kByU64, kStamps, kDefer>(img, smem, n, out, cap, dbg, lane, 0, pp, rec, rlim);
+}
+
+// Deferred emit (flush_records) where the kernel is built for it (kRecords),
+// the launch has a record buffer and the block's output is unlimited.
+template <bool kStamps, bool kRecords, class IMG>
+LZ4E_DEV CResult dispatch_emit(const IMG& img, uint32_t* smem, uint32_t n, int tt, gu8* out,
+                               uint32_t cap, uint64_t* dbg, uint32_t lane, uint32_t D, bool pp,
+                               uint64_t* records, uint32_t nrecords, uint32_t b) {
+    if constexpr (kRecords) {
+        const uint64_t bound = (uint64_t)n + n / 255 + 16;
+        if (records != nullptr && cap >= bound && n < (1u << kRecLenBits))
+            return dispatch_class<kStamps, true>(img, smem, n, tt, out, cap, dbg, lane, D, pp,
+                                                 (gu64*)(records + (size_t)b * nrecords), nrecords - kWave);
+    }
+    return dispatch_class<kStamps, false>(img, smem, n, tt, out, cap, dbg, lane, D, pp, nullptr, 0);
 }
 
 // The kernel's explicit arguments as laid out in the kernarg segment
@@ -1163,10 +1317,17 @@ struct CompressArgs {
     uint64_t* dbg;
     const uint32_t* dict_len;
     const uint32_t* order;
+    uint64_t* records;
+    uint32_t nrecords;
 };
-static_assert(offsetof(CompressArgs, ret) == 56 && offsetof(CompressArgs, order) == 96, "kernarg layout");
+static_assert(offsetof(CompressArgs, ret) == 56 && offsetof(CompressArgs, order) == 96 &&
+                  offsetof(CompressArgs, nrecords) == 112,
+              "kernarg layout");
 
-template <bool kLdsInput, bool kStamps>
+// records: the launch's record buffer, nrecords (a power of two, >= 64) slots
+// per block, or null (every block emits inline); kRecords: built with the
+// deferred emit.
+template <bool kLdsInput, bool kStamps, bool kRecords>
 __global__ __launch_bounds__(64) void compress_kernel(const uint8_t* __restrict__ src,
                                                       const uint64_t* __restrict__ src_off,
                                                       const uint32_t* __restrict__ src_len,
@@ -1178,7 +1339,8 @@ __global__ __launch_bounds__(64) void compress_kernel(const uint8_t* __restrict_
                                                       uint32_t* __restrict__ aux, uint32_t nblocks,
                                                       uint32_t max_len, uint64_t* __restrict__ dbg,
                                                       const uint32_t* __restrict__ dict_len,
-                                                      const uint32_t* __restrict__ order) {
+                                                      const uint32_t* __restrict__ order,
+                                                      uint64_t* records, uint32_t nrecords) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     if (blockIdx.x >= nblocks) return;
     const uint32_t b = order ? order[blockIdx.x] : blockIdx.x;
@@ -1218,7 +1380,8 @@ __global__ __launch_bounds__(64) void compress_kernel(const uint8_t* __restrict_
         stage_block(inw, in, n, lane);
         block_sync();
         const LdsImage img{inw, n == 0 ? 0 : (n - 1) >> 2};
-        res = dispatch_class<kStamps>(img, smem, n, tt, out, cap, dbg_slot, lane);
+        res = dispatch_emit<kStamps, kRecords>(img, smem, n, tt, out, cap, dbg_slot, lane, 0, true, records,
+                                               nrecords, b);
     } else {
         block_sync();
         const uint8_t* base = in - D;
@@ -1245,7 +1408,8 @@ __global__ __launch_bounds__(64) void compress_kernel(const uint8_t* __restrict_
                 if (blockIdx.x < nh) __builtin_amdgcn_s_setprio(3);
             }
         }
-        res = dispatch_class<kStamps>(img, smem, n, tt, out, cap, dbg_slot, lane, D, pp);
+        res = dispatch_emit<kStamps, kRecords>(img, smem, n, tt, out, cap, dbg_slot, lane, D, pp, records,
+                                               nrecords, b);
     }
     // results, through pointers reloaded now (see CompressArgs)
 #ifndef LZ4E_EMU
@@ -1388,6 +1552,72 @@ uint32_t env_u32(const char* name, uint32_t dflt) {
     return e ? (uint32_t)strtoul(e, nullptr, 10) : dflt;
 }
 
+// Record slots per block of the deferred emit: a power of two in
+// kRecMin..kRecMax, at most LZ4E_COMPRESS_RECORDS (read per call; tests and
+// A/B runs; 0: no record buffer, every block emits inline) and small enough
+// that the launch's buffer stays within kRecBudget; 0 when even kRecMin slots
+// per block would not.  A block flushes once fewer than 64 slots are free, so
+// kRecMin flushes every window that found a sequence.
+constexpr uint32_t kRecMin = kWave, kRecMax = 4096, kRecDefault = 1024;
+constexpr size_t kRecBudget = (size_t)64 << 20;
+uint32_t record_slots(uint32_t nblocks) {
+    const char* e = getenv("LZ4E_COMPRESS_RECORDS");
+    const uint32_t want = e ? (uint32_t)strtoul(e, nullptr, 10) : kRecDefault;
+    if (want == 0) return 0;
+    uint32_t r = kRecMin;
+    while (2 * r <= want && 2 * r <= kRecMax) r *= 2;
+    while (r > kRecMin && sizeof(uint64_t) * (size_t)nblocks * r > kRecBudget) r /= 2;
+    return sizeof(uint64_t) * (size_t)nblocks * r <= kRecBudget ? r : 0;
+}
+// The launch's stream-ordered allocation.  The device's default pool returns
+// freed memory to the system at the next synchronize (release threshold 0),
+// so a launch that follows one would wait for a fresh mapping of its record
+// buffer (~0.2 ms for 25 MiB) with the GPU idle.  A pool of the library's own
+// per device keeps up to kRecBudget + 1 MiB between launches instead; where
+// it cannot be had, the default pool serves.
+#ifndef LZ4E_EMU
+hipError_t launch_alloc(void** p, size_t bytes, hipStream_t stream) {
+    constexpr int kMaxDevices = 64;
+    static std::mutex mu;
+    static hipMemPool_t pools[kMaxDevices];
+    static bool tried[kMaxDevices];
+    int dev = -1;
+    hipMemPool_t pool = nullptr;
+    if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxDevices) {
+        std::lock_guard<std::mutex> lk(mu);
+        if (!tried[dev]) {
+            tried[dev] = true;
+            hipMemPoolProps props = {};
+            props.allocType = hipMemAllocationTypePinned;
+            props.handleTypes = hipMemHandleTypeNone;
+            props.location.type = hipMemLocationTypeDevice;
+            props.location.id = dev;
+            uint64_t keep = kRecBudget + ((uint64_t)1 << 20);
+            if (hipMemPoolCreate(&pools[dev], &props) != hipSuccess ||
+                hipMemPoolSetAttribute(pools[dev], hipMemPoolAttrReleaseThreshold, &keep) != hipSuccess) {
+                (void)hipGetLastError();
+                pools[dev] = nullptr;
+            }
+        }
+        pool = pools[dev];
+    }
+    if (pool != nullptr && hipMallocFromPoolAsync(p, bytes, pool, stream) == hipSuccess) return hipSuccess;
+    (void)hipGetLastError();
+    return hipMallocAsync(p, bytes, stream);
+}
+#else
+hipError_t launch_alloc(void** p, size_t bytes, hipStream_t stream) { return hipMallocAsync(p, bytes, stream); }
+#endif
+
+// The LDS-image kernel (blocks of <= kMaxLdsInput bytes) emits inline; the
+// lane emulator builds it with the deferred emit as well, so that its small
+// planted blocks run the record and flush code of every table class.
+#ifdef LZ4E_EMU
+constexpr bool kDeferLds = true;
+#else
+constexpr bool kDeferLds = false;
+#endif
+
 template <bool kStamps>
 hipError_t launch_compress_impl(const CompressBatch& a, hipStream_t stream, uint64_t* dbg) {
     if (a.nblocks == 0) return hipSuccess;
@@ -1396,34 +1626,42 @@ hipError_t launch_compress_impl(const CompressBatch& a, hipStream_t stream, uint
     const bool lds_input = a.max_len <= lds_max && a.dict_len == nullptr;
     const dim3 grid(a.nblocks), block(kWave);
     const uint32_t lds = compress_lds_bytes(a.max_len, lds_input);
-    if (lds_input) {
-        hipLaunchKernelGGL((compress_kernel<true, kStamps>), grid, block, lds, stream, a.src,
-                           a.src_off, a.src_len, a.table_type, a.dst, a.dst_off, a.dst_cap, a.ret,
-                           a.aux, a.nblocks, a.max_len, dbg, a.dict_len, nullptr);
-        return hipGetLastError();
-    }
     // heavy blocks first (see weight_kernel)
     const int om = launch_order_mode(true);
-    const bool use_order = om == kOrderAlways ||
-                           (om == kOrderAuto && a.nblocks >= kOrderMinBlocks && a.max_len >= kOrderMinLen);
-    uint32_t* scratch = nullptr;
-    if (use_order &&
-        hipMallocAsync((void**)&scratch, sizeof(uint32_t) * (2 * (size_t)a.nblocks + 1), stream) == hipSuccess) {
-        hipLaunchKernelGGL(weight_kernel, dim3(a.nblocks), dim3(kWeightThreads), 0, stream, a.src,
-                           a.src_off, a.src_len, a.nblocks, scratch);
-        hipLaunchKernelGGL((order_kernel<CompressWeight>), dim3(1), dim3(kOrderThreads), 0, stream,
-                           CompressWeight{scratch}, a.nblocks, scratch + a.nblocks, kHeavyBucket,
-                           scratch + 2 * (size_t)a.nblocks);
-    } else {
-        (void)hipGetLastError();  // a failed pool allocation only costs the ordering
-        scratch = nullptr;
+    const bool use_order = !lds_input && (om == kOrderAlways || (om == kOrderAuto && a.nblocks >= kOrderMinBlocks &&
+                                                                 a.max_len >= kOrderMinLen));
+    // One stream-ordered allocation: the record buffer of the deferred emit
+    // (nblocks x nrec x 8 bytes), then the launch order's scratch.
+    const uint32_t nrec = (!lds_input || kDeferLds) ? record_slots(a.nblocks) : 0;
+    const size_t rec_bytes = sizeof(uint64_t) * (size_t)a.nblocks * nrec;
+    const size_t order_bytes = use_order ? sizeof(uint32_t) * (2 * (size_t)a.nblocks + 1) : 0;
+    uint8_t* pool = nullptr;
+    if (rec_bytes + order_bytes != 0 &&
+        launch_alloc((void**)&pool, rec_bytes + order_bytes, stream) != hipSuccess) {
+        (void)hipGetLastError();  // a failed pool allocation costs the ordering and the deferred emit
+        pool = nullptr;
     }
-    hipLaunchKernelGGL((compress_kernel<false, kStamps>), grid, block, lds, stream, a.src,
-                       a.src_off, a.src_len, a.table_type, a.dst, a.dst_off, a.dst_cap, a.ret,
-                       a.aux, a.nblocks, a.max_len, dbg, a.dict_len,
-                       scratch ? (const uint32_t*)(scratch + a.nblocks) : nullptr);
+    uint64_t* records = pool && nrec ? (uint64_t*)pool : nullptr;
+    uint32_t* scratch = pool && use_order ? (uint32_t*)(pool + rec_bytes) : nullptr;
+    if (lds_input) {
+        hipLaunchKernelGGL((compress_kernel<true, kStamps, kDeferLds>), grid, block, lds, stream, a.src,
+                           a.src_off, a.src_len, a.table_type, a.dst, a.dst_off, a.dst_cap, a.ret,
+                           a.aux, a.nblocks, a.max_len, dbg, a.dict_len, nullptr, records, nrec);
+    } else {
+        if (scratch) {
+            hipLaunchKernelGGL(weight_kernel, dim3(a.nblocks), dim3(kWeightThreads), 0, stream, a.src,
+                               a.src_off, a.src_len, a.nblocks, scratch);
+            hipLaunchKernelGGL((order_kernel<CompressWeight>), dim3(1), dim3(kOrderThreads), 0, stream,
+                               CompressWeight{scratch}, a.nblocks, scratch + a.nblocks, kHeavyBucket,
+                               scratch + 2 * (size_t)a.nblocks);
+        }
+        hipLaunchKernelGGL((compress_kernel<false, kStamps, true>), grid, block, lds, stream, a.src,
+                           a.src_off, a.src_len, a.table_type, a.dst, a.dst_off, a.dst_cap, a.ret,
+                           a.aux, a.nblocks, a.max_len, dbg, a.dict_len,
+                           scratch ? (const uint32_t*)(scratch + a.nblocks) : nullptr, records, nrec);
+    }
     const hipError_t err = hipGetLastError();
-    if (scratch) (void)hipFreeAsync(scratch, stream);
+    if (pool) (void)hipFreeAsync(pool, stream);
     return err;
 }
 

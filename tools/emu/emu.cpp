@@ -18,6 +18,10 @@ alignas(16) uint32_t smem[(16384 + 65536 + 64) / 4];
 #include "lz4e_compress.hip"
 
 // The emulator launches in block order (no pool for the order's scratch).
+// The launch's record buffer (deferred emit) is a heap block of its exact
+// size here, and under LZ4E_EMU the LDS-image kernel gets one as well:
+// unlimited blocks of any size record and flush by default
+// (LZ4E_COMPRESS_RECORDS / emu_main --ring N sets the slots per block, 0 none).
 namespace lz4e {
 int launch_order_mode(bool) { return kOrderNever; }
 }  // namespace lz4e

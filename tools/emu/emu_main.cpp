@@ -22,6 +22,9 @@
 // (default: the block's bound, n + n/255 + 16), so ASan and the canary see any
 // store outside a limited output; a block that is refused (ret 0) writes no
 // FRAME_OUT.
+// A leading "--ring N" gives the compressor N record slots per block for its
+// deferred emit (LZ4E_COMPRESS_RECORDS; 0: none, every block emits inline;
+// default: the library's).
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -138,8 +141,13 @@ static int decode_main(int argc, char** argv) {
 
 int main(int argc, char** argv) {
     long cap_arg = -1;
-    while (argc > 2 && (!strcmp(argv[1], "--skew") || !strcmp(argv[1], "--cap"))) {
-        if (!strcmp(argv[1], "--cap")) {
+    while (argc > 2 && (!strcmp(argv[1], "--skew") || !strcmp(argv[1], "--cap") || !strcmp(argv[1], "--ring"))) {
+        if (!strcmp(argv[1], "--ring")) {
+            char* end = nullptr;
+            const long ring = strtol(argv[2], &end, 10);
+            if (!*argv[2] || *end || ring < 0 || ring > 4096) return 2;
+            setenv("LZ4E_COMPRESS_RECORDS", argv[2], 1);
+        } else if (!strcmp(argv[1], "--cap")) {
             char* end = nullptr;
             cap_arg = strtol(argv[2], &end, 10);
             if (!*argv[2] || *end || cap_arg < 0 || cap_arg > 0x7FFFFFFFL) return 2;
@@ -156,7 +164,7 @@ int main(int argc, char** argv) {
         (argv[1][1] == 'd' || argv[1][1] == 'p' || argv[1][1] == 'l' || argv[1][1] == 'g' || argv[1][1] == 'G'))
         return decode_main(argc, argv);
     if (argc < 3) {
-        fprintf(stderr, "usage: emu_main [--skew S,D] [--cap N] BLOCK_FILE TABLE_CLASS [FRAME_OUT [DICT_FILE]]\n");
+        fprintf(stderr, "usage: emu_main [--skew S,D] [--cap N] [--ring N] BLOCK_FILE TABLE_CLASS [FRAME_OUT [DICT_FILE]]\n");
         return 2;
     }
     FILE* f = fopen(argv[1], "rb");
