@@ -431,6 +431,79 @@ int lz4e_chunk_write_batch(struct lz4e_chunk_request *reqs, int n,
 int lz4e_register_host_memory(void *ptr, size_t len);
 int lz4e_unregister_host_memory(void *ptr);
 
+/*
+ * Packed frame store: keeping the compressed bytes.
+ *
+ * lz4e_compress_batch_dev leaves frame i in a slot of the caller's choosing
+ * (LZ4E_COMPRESSBOUND bytes for a compress that cannot fail), so after it the
+ * frames occupy more memory than the input did.  lz4e_pack_batch_dev compacts
+ * them into one dense image with an index and stores raw every block that did
+ * not shrink; lz4e_unpack_batch_dev decodes such an image back into blocks.
+ *
+ * All pointers are device pointers.  frames / fr_off / ret are the dst /
+ * dst_off / ret arrays and src / src_off / src_len the input arrays of the
+ * lz4e_compress_batch_dev call that came before on the same stream; max_len
+ * bounds src_len[] (src_len[i] <= LZ4E_MAX_INPUT_SIZE).  Both calls only
+ * launch work on `stream` and are legal under stream capture: no synchronise,
+ * no host read of device data, no hipMalloc / hipFree / hipMemcpy (pack uses
+ * no scratch memory at all, unpack nblocks words from the stream-ordered
+ * pool).  Both return 0 on a successful launch and -1 on a HIP failure, with
+ * lz4e_last_error() set.  lz4e_pack_batch_dev returns -22 (-EINVAL) without
+ * launching anything for an `align` that is 0, above 4096 or not a power of
+ * two.
+ *
+ * Pack, per block i:
+ *   kind     LZ4E_PACK_FRAME with pk_len[i] = ret[i] when
+ *            0 < ret[i] < src_len[i]; otherwise LZ4E_PACK_RAW with
+ *            pk_len[i] = src_len[i]: a failed compress (ret == 0), a frame
+ *            that is not smaller than its input (equality included), an
+ *            empty block.
+ *   offsets  pk_off[0] = 0, pk_off[i + 1] = pk_off[i] + roundup(pk_len[i],
+ *            align); 64-bit; pk_off[nblocks] is the stored size.
+ *   bytes    packed[pk_off[i], pk_off[i] + pk_len[i]) is the frame or the raw
+ *            input; the padding up to pk_off[i + 1] is written as zeros, so
+ *            packed[0, pk_off[nblocks]) is a pure function of the inputs (it
+ *            can be checksummed, deduplicated and compared whole).
+ *   index    pk_off, pk_len and pk_kind are written whatever packed_cap is:
+ *            a caller sizes a buffer from pk_off[nblocks].
+ *   all or nothing
+ *            if pk_off[nblocks] > packed_cap no byte of `packed` is written;
+ *            otherwise no byte at or past pk_off[nblocks] is written.
+ *   reads    stay inside [frames + fr_off[i], + ret[i]) for a frame entry and
+ *            inside [src + src_off[i], + src_len[i]) for a raw one, exactly
+ *            (not rounded to words); a raw block's frame slot and a frame
+ *            block's source are not read.
+ *   aliasing `packed` overlaps neither `frames` nor `src`.
+ *   nblocks == 0: pk_off[0] = 0 and nothing else happens.
+ *
+ * Unpack, per block i (max_cap bounds dst_cap[], 0 = unknown):
+ *   LZ4E_PACK_FRAME  ret[i] and the bytes at dst + dst_off[i] are what
+ *            lz4e_decompress_batch_dev2 gives for a frame of pk_len[i] bytes
+ *            at packed + pk_off[i] with capacity dst_cap[i], error codes
+ *            included; the decoder is chosen from max_cap and nblocks by the
+ *            same rule and LZ4E_DECOMPRESS_MODE is honoured.
+ *   LZ4E_PACK_RAW    pk_len[i] <= dst_cap[i]: the pk_len[i] bytes are copied
+ *            and ret[i] = pk_len[i]; otherwise ret[i] = -1 and nothing is
+ *            written.
+ *   any other kind   ret[i] = -1 and nothing is written.
+ *   writes   stay inside [dst_off[i], dst_off[i] + dst_cap[i]).
+ * pk_off needs no alignment: the decoders take frames at any byte address.
+ */
+#define LZ4E_PACK_FRAME 0   /* entry holds an LZ4E frame                    */
+#define LZ4E_PACK_RAW   1   /* entry holds the block's input bytes verbatim */
+int lz4e_pack_batch_dev(const uint8_t *frames, const uint64_t *fr_off,
+			const int32_t *ret, const uint8_t *src,
+			const uint64_t *src_off, const uint32_t *src_len,
+			uint8_t *packed, uint64_t packed_cap, uint32_t align,
+			uint64_t *pk_off /* nblocks + 1 */, int32_t *pk_len,
+			uint8_t *pk_kind, uint32_t nblocks, uint32_t max_len,
+			void *stream);
+int lz4e_unpack_batch_dev(const uint8_t *packed, const uint64_t *pk_off,
+			  const int32_t *pk_len, const uint8_t *pk_kind,
+			  uint8_t *dst, const uint64_t *dst_off,
+			  const int32_t *dst_cap, int32_t *ret, uint32_t nblocks,
+			  uint32_t max_cap, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

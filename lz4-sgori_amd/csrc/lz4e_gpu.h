@@ -112,4 +112,49 @@ struct SgDeliverBatch {
 };
 hipError_t launch_sg_deliver(const SgDeliverBatch& a, hipStream_t stream);
 
+// Packed frame store (lz4e_pack.hip; include/lz4e.h lz4e_pack_batch_dev /
+// lz4e_unpack_batch_dev).  Entry kinds as in the public header.
+constexpr uint32_t kPackFrame = 0, kPackRaw = 1;
+// Blocks per scan tile: one per thread of a 256-thread workgroup; the one
+// wave that scans the tile sums takes 64 of them per round.
+constexpr uint32_t kPackTile = 256;
+struct PackBatch {
+    const uint8_t* frames;  // the compress launch's dst / dst_off / ret
+    const uint64_t* fr_off;
+    const int32_t* ret;
+    const uint8_t* src;  // and its src / src_off / src_len
+    const uint64_t* src_off;
+    const uint32_t* src_len;
+    uint8_t* packed;
+    uint64_t packed_cap;
+    uint32_t align;    // power of two, 1..4096 (checked by the caller)
+    uint64_t* pk_off;  // nblocks + 1
+    int32_t* pk_len;
+    uint8_t* pk_kind;
+    uint32_t nblocks;
+    uint32_t max_len;  // upper bound of src_len[] (sizes the copy's grid)
+};
+// Index (three launches: tile sums, scan of the tile sums, tile scan + base)
+// and the gather; no scratch memory: the tile sums live in pk_off itself.
+hipError_t launch_pack(const PackBatch& a, hipStream_t stream);
+// masked[i] = pk_len[i] for a frame entry, 0 for every other kind: the
+// decoders then return -1 for it and touch neither its input nor its output.
+hipError_t launch_unpack_mask(const int32_t* pk_len, const uint8_t* pk_kind, uint32_t nblocks,
+                              int32_t* masked, hipStream_t stream);
+// Behind the decoders: the raw entries' bytes, and ret of every entry that is
+// not a frame.
+struct UnpackRawBatch {
+    const uint8_t* packed;
+    const uint64_t* pk_off;
+    const int32_t* pk_len;
+    const uint8_t* pk_kind;
+    uint8_t* dst;
+    const uint64_t* dst_off;
+    const int32_t* dst_cap;
+    int32_t* ret;
+    uint32_t nblocks;
+    uint32_t max_cap;  // upper bound of dst_cap[] (0: unknown)
+};
+hipError_t launch_unpack_raw(const UnpackRawBatch& a, hipStream_t stream);
+
 }  // namespace lz4e

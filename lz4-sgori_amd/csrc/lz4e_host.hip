@@ -960,6 +960,44 @@ int lz4e_decompress_batch_dev_dict(const uint8_t* src, const uint64_t* src_off, 
                : -1;
 }
 
+// Packed frame store (lz4e_pack.hip).  Launches only: legal under stream
+// capture.  Pack needs no scratch (its tile sums live in pk_off); unpack's
+// masked length array comes from the stream-ordered pool, as the decoders'
+// own scratch does.
+int lz4e_pack_batch_dev(const uint8_t* frames, const uint64_t* fr_off, const int32_t* ret,
+                        const uint8_t* src, const uint64_t* src_off, const uint32_t* src_len,
+                        uint8_t* packed, uint64_t packed_cap, uint32_t align, uint64_t* pk_off,
+                        int32_t* pk_len, uint8_t* pk_kind, uint32_t nblocks, uint32_t max_len,
+                        void* stream) {
+    g_err.clear();
+    if (align == 0 || align > 4096 || (align & (align - 1)) != 0) {
+        set_err("lz4e_pack_batch_dev: align must be a power of two from 1 to 4096");
+        return -22;
+    }
+    lz4e::PackBatch a{frames, fr_off, ret, src, src_off, src_len, packed, packed_cap, align, pk_off,
+                      pk_len, pk_kind, nblocks, max_len};
+    return hip_ok(lz4e::launch_pack(a, static_cast<hipStream_t>(stream)), "pack launch") ? 0 : -1;
+}
+
+int lz4e_unpack_batch_dev(const uint8_t* packed, const uint64_t* pk_off, const int32_t* pk_len,
+                          const uint8_t* pk_kind, uint8_t* dst, const uint64_t* dst_off,
+                          const int32_t* dst_cap, int32_t* ret, uint32_t nblocks, uint32_t max_cap,
+                          void* stream) {
+    g_err.clear();
+    if (nblocks == 0) return 0;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    int32_t* masked = nullptr;
+    if (!hip_ok(hipMallocAsync((void**)&masked, sizeof(int32_t) * (size_t)nblocks, s), "unpack scratch"))
+        return -1;
+    lz4e::DecompressBatch d{packed, pk_off, masked, dst, dst_off, dst_cap, ret, nblocks, max_cap};
+    lz4e::UnpackRawBatch r{packed, pk_off, pk_len, pk_kind, dst, dst_off, dst_cap, ret, nblocks, max_cap};
+    const bool ok = hip_ok(lz4e::launch_unpack_mask(pk_len, pk_kind, nblocks, masked, s), "unpack mask launch") &&
+                    hip_ok(lz4e::launch_decompress(d, s), "unpack decompress launch") &&
+                    hip_ok(lz4e::launch_unpack_raw(r, s), "unpack raw launch");
+    (void)hipFreeAsync(masked, s);
+    return ok ? 0 : -1;
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------

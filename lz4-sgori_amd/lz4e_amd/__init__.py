@@ -32,6 +32,7 @@ __all__ = [
     "decompress_batch", "compress_batch_dev", "decompress_batch_dev",
     "GpuUnavailable", "LIB_PATH", "EXPORTED_SYMBOLS", "HostArena", "GuardReport",
     "register_host_memory", "unregister_host_memory", "zero_copy_requests",
+    "pack_batch_dev", "unpack_batch_dev", "PACK_FRAME", "PACK_RAW",
 ]
 
 PAGE_SIZE = 4096
@@ -52,6 +53,7 @@ EXPORTED_SYMBOLS = (
     "LZ4E_compress_usingDict", "LZ4E_decompress_safe_usingDict", "lz4e_compress_sg_batch_dict",
     "lz4e_decompress_batch_dict", "lz4e_compress_batch_dev_dict", "lz4e_decompress_batch_dev_dict",
     "lz4e_register_host_memory", "lz4e_unregister_host_memory",
+    "lz4e_pack_batch_dev", "lz4e_unpack_batch_dev",
 )
 
 
@@ -169,6 +171,11 @@ def lib() -> ctypes.CDLL:
         L.lz4e_unregister_host_memory.restype = I32
         L.lz4e_debug_chunk_zero_copy_requests.argtypes = []
         L.lz4e_debug_chunk_zero_copy_requests.restype = ctypes.c_uint64
+    if hasattr(L, "lz4e_pack_batch_dev"):
+        L.lz4e_pack_batch_dev.argtypes = [P] * 7 + [ctypes.c_uint64, U32, P, P, P, U32, U32, P]
+        L.lz4e_pack_batch_dev.restype = I32
+        L.lz4e_unpack_batch_dev.argtypes = [P] * 8 + [U32, U32, P]
+        L.lz4e_unpack_batch_dev.restype = I32
     _lib = L
     return L
 
@@ -603,9 +610,11 @@ def _check_dev(n: int, **tensors) -> None:
     import torch
     want = {"src": torch.uint8, "dst": torch.uint8, "table_type": torch.uint8,
             "src_off": torch.int64, "dst_off": torch.int64, "src_len": torch.int32,
-            "dst_cap": torch.int32, "ret": torch.int32, "aux": torch.int32}
+            "dst_cap": torch.int32, "ret": torch.int32, "aux": torch.int32,
+            "frames": torch.uint8, "fr_off": torch.int64, "packed": torch.uint8,
+            "pk_off": torch.int64, "pk_len": torch.int32, "pk_kind": torch.uint8}
     per_block = {"src_off": 1, "dst_off": 1, "src_len": 1, "dst_cap": 1, "ret": 1,
-                 "table_type": 1, "aux": 2}
+                 "table_type": 1, "aux": 2, "fr_off": 1, "pk_len": 1, "pk_kind": 1}
     dev = None
     for name, t in tensors.items():
         if t is None:
@@ -622,6 +631,8 @@ def _check_dev(n: int, **tensors) -> None:
             raise ValueError(f"{name}: on {t.device}, other tensors on {dev}")
         if name in per_block and t.numel() < per_block[name] * n:
             raise ValueError(f"{name}: {t.numel()} entries for {n} blocks")
+        if name == "pk_off" and t.numel() < n + 1:
+            raise ValueError(f"pk_off: {t.numel()} entries for {n} blocks (needs {n + 1})")
 
 
 def compress_batch_dev(src, src_off, src_len, table_type_, dst, dst_off, dst_cap, ret,
@@ -668,3 +679,56 @@ def decompress_batch_dev(src, src_off, src_len, dst, dst_off, dst_cap, ret, stre
                                          max(0, int(max_cap)), stream)
     if r != 0:
         raise RuntimeError("lz4e_decompress_batch_dev2: " + last_error())
+
+
+PACK_FRAME, PACK_RAW = 0, 1
+
+
+def pack_batch_dev(frames, fr_off, ret, src, src_off, src_len, packed, pk_off, pk_len, pk_kind,
+                   align: int = 1, packed_cap: Optional[int] = None, max_len: Optional[int] = None,
+                   stream=None) -> None:
+    """lz4e_pack_batch_dev on torch tensors (launch only).
+
+    frames / fr_off / ret and src / src_off / src_len are the dst / dst_off /
+    ret and input tensors of the compress_batch_dev call before it.  packed:
+    uint8 (``packed_cap`` defaults to its size); pk_off: int64 [nblocks + 1];
+    pk_len: int32; pk_kind: uint8.  ``max_len`` bounds src_len (default: read
+    from it, which synchronises).  A bad ``align`` raises ValueError."""
+    import torch
+    n = int(src_len.numel())
+    _check_dev(n, frames=frames, fr_off=fr_off, ret=ret, src=src, src_off=src_off, src_len=src_len,
+               packed=packed, pk_off=pk_off, pk_len=pk_len, pk_kind=pk_kind)
+    if packed_cap is None:
+        packed_cap = int(packed.numel())
+    if packed_cap < 0 or packed_cap > packed.numel():
+        raise ValueError(f"packed_cap {packed_cap} for a tensor of {packed.numel()} bytes")
+    if max_len is None:
+        max_len = int(src_len.max().item()) if n else 0
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    r = lib().lz4e_pack_batch_dev(_ptr(frames), _ptr(fr_off), _ptr(ret), _ptr(src), _ptr(src_off),
+                                  _ptr(src_len), _ptr(packed), int(packed_cap), int(align), _ptr(pk_off),
+                                  _ptr(pk_len), _ptr(pk_kind), n, int(max_len), stream)
+    if r == -22:
+        raise ValueError("lz4e_pack_batch_dev: " + last_error())
+    if r != 0:
+        raise RuntimeError("lz4e_pack_batch_dev: " + last_error())
+
+
+def unpack_batch_dev(packed, pk_off, pk_len, pk_kind, dst, dst_off, dst_cap, ret, stream=None,
+                     max_cap: Optional[int] = None) -> None:
+    """lz4e_unpack_batch_dev on torch tensors (launch only).  ``max_cap``
+    bounds dst_cap and selects the decoder as in decompress_batch_dev
+    (default: read from it, which synchronises)."""
+    import torch
+    n = int(pk_len.numel())
+    _check_dev(n, packed=packed, pk_off=pk_off, pk_len=pk_len, pk_kind=pk_kind, dst=dst, dst_off=dst_off,
+               dst_cap=dst_cap, ret=ret)
+    if max_cap is None:
+        max_cap = int(dst_cap.max().item()) if n else 0
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    r = lib().lz4e_unpack_batch_dev(_ptr(packed), _ptr(pk_off), _ptr(pk_len), _ptr(pk_kind), _ptr(dst),
+                                    _ptr(dst_off), _ptr(dst_cap), _ptr(ret), n, max(0, int(max_cap)), stream)
+    if r != 0:
+        raise RuntimeError("lz4e_unpack_batch_dev: " + last_error())

@@ -7,6 +7,9 @@
 #   EMU_EXE=1 tools/emu/build.sh [flags] -> $EMU_BUILD/emu_main (standalone)
 #   EMU_SG=1 tools/emu/build.sh [flags]  -> $EMU_BUILD/emu_sg (standalone: the
 #                                           zero-copy kernels of csrc/lz4e_sg.hip)
+#   EMU_PACK=1 tools/emu/build.sh [flags] -> $EMU_BUILD/emu_pack (standalone: the
+#                                           packed frame store's kernels,
+#                                           csrc/lz4e_pack.hip)
 # Pass extra flags, e.g. -fsanitize=address,undefined or -DLZ4E_SPIN_MAX=1.
 set -e
 here=$(cd "$(dirname "$0")" && pwd)
@@ -15,7 +18,10 @@ b="${EMU_BUILD:-$here/build}"
 mkdir -p "$b"
 CXX=${CXX:-/opt/rocm/llvm/bin/clang++}
 FLAGS=(-std=c++20 -O1 -g -pthread -x c++ -DLZ4E_EMU -I "$here/include" -I "$csrc")
-if [ -n "$EMU_SG" ]; then
+if [ -n "$EMU_PACK" ]; then
+    $CXX "${FLAGS[@]}" -I "$here/../../include" "$@" "$here/emu_pack.cpp" -o "$b/emu_pack"
+    echo "built $b/emu_pack"
+elif [ -n "$EMU_SG" ]; then
     $CXX "${FLAGS[@]}" -I "$here/../../include" "$@" "$here/emu_sg.cpp" -o "$b/emu_sg"
     echo "built $b/emu_sg"
 elif [ -n "$EMU_EXE" ]; then

@@ -1,0 +1,430 @@
+// Lane emulator of the packed frame store's kernels (debug/test tooling,
+// tools/emu): compiles the unmodified csrc/lz4e_pack.hip as host C++ and runs
+// the four pack kernels, unpack_mask_kernel and unpack_raw_kernel with every
+// lane a host thread, under the same emulated <hip/hip_runtime.h> as the other
+// kernel files (the decoders that run between the two unpack kernels are
+// emu_main's business).  Stand-alone (its own main): built by
+// EMU_PACK=1 build.sh, run by tests/test_emulator_pack.py under ASan + UBSan.
+//
+// The kernels work on the CALLER's memory at byte granularity.  So every
+// frame slot, every source block, `packed`, every unpack destination and
+// every index array here is its own heap allocation that ends exactly at the
+// last byte the contract allows (ASan's redzone follows it), placed at a
+// chosen alignment mod 16 as in emu_sg.cpp: the whole 8-byte granules of the
+// prefix are poisoned, the up to 7 bytes left hold a canary.  A frame entry's
+// source and a raw entry's frame slot are allocations of 0 bytes: reading
+// them at all is a report.
+//
+// The scan kernels use cross-lane operations and workgroup barriers, so a
+// workgroup of theirs is 256 host threads (4 emulated waves) that live as
+// long as the program (the one-wave scan of the tile sums: 64 threads of its
+// own); workgroups run one after the other.  The copy, mask
+// and raw-copy kernels have neither, so their lanes run one after the other
+// on the calling thread (the launch macro below hands the kernel's name on).
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <memory>
+#include <thread>
+#include <vector>
+
+#include <hip/hip_runtime.h>
+#undef __shared__
+#define __shared__ static
+void emu_launch_named(const char* kernel, uint32_t nblocks, uint32_t threads, std::function<void()> body);
+#undef hipLaunchKernelGGL
+#define hipLaunchKernelGGL(k, grid, block, lds, stream, ...) \
+    emu_launch_named(#k, (grid).x, (block).x, [&]() { k(__VA_ARGS__); })
+
+#include "lz4e_pack.hip"
+
+#include "lz4e.h"
+
+#if defined(__has_feature)
+#if __has_feature(address_sanitizer)
+#include <sanitizer/asan_interface.h>
+#define EMU_POISON(p, n) __asan_poison_memory_region((p), (n))
+#define EMU_UNPOISON(p, n) __asan_unpoison_memory_region((p), (n))
+#endif
+#endif
+#ifndef EMU_POISON
+#define EMU_POISON(p, n) ((void)0)
+#define EMU_UNPOISON(p, n) ((void)0)
+#endif
+
+thread_local EmuWave* g_emu_wave;
+thread_local uint32_t g_emu_lane;
+thread_local EmuBarrier* g_emu_group;
+dim3 blockIdx, gridDim;
+thread_local dim3 threadIdx;
+
+namespace {
+constexpr uint32_t kLanes = 256;  // the tile kernels' workgroup
+struct LanePool {
+    EmuBarrier start{kLanes + 1}, end{kLanes + 1}, group{kLanes};
+    EmuWave waves[kLanes / 64];
+    std::function<void()>* body = nullptr;
+    bool quit = false;
+    std::vector<std::thread> th;
+    LanePool() {
+        for (uint32_t t = 0; t < kLanes; ++t)
+            th.emplace_back([this, t]() {
+                g_emu_wave = &waves[t / 64];
+                g_emu_lane = t % 64;
+                g_emu_group = &group;
+                threadIdx = dim3(t);
+                for (;;) {
+                    start.arrive_and_wait();
+                    if (quit) return;
+                    (*body)();
+                    end.arrive_and_wait();
+                }
+            });
+    }
+    ~LanePool() {
+        quit = true;
+        start.arrive_and_wait();
+        for (auto& x : th) x.join();
+    }
+};
+}  // namespace
+
+void emu_launch(uint32_t nblocks, uint32_t threads, std::function<void()> body) {
+    gridDim = dim3(nblocks);
+    if (threads == 64 && nblocks == 1) {  // pack_tile_scan_kernel
+        EmuWave wave;
+        blockIdx = dim3(0);
+        std::vector<std::thread> th;
+        for (uint32_t t = 0; t < 64; ++t)
+            th.emplace_back([&, t]() {
+                g_emu_wave = &wave;
+                g_emu_lane = t;
+                threadIdx = dim3(t);
+                body();
+            });
+        for (auto& x : th) x.join();
+        return;
+    }
+    static LanePool pool;
+    if (threads != kLanes) abort();
+    pool.body = &body;
+    for (uint32_t b = 0; b < nblocks; ++b) {
+        blockIdx = dim3(b);
+        pool.start.arrive_and_wait();
+        pool.end.arrive_and_wait();
+    }
+}
+
+void emu_launch_named(const char* kernel, uint32_t nblocks, uint32_t threads, std::function<void()> body) {
+    if (strstr(kernel, "pack_tile") || strstr(kernel, "pack_index")) return emu_launch(nblocks, threads, body);
+    gridDim = dim3(nblocks);
+    for (uint32_t b = 0; b < nblocks; ++b) {
+        blockIdx = dim3(b);
+        for (uint32_t t = 0; t < threads; ++t) {
+            threadIdx = dim3(t);
+            g_emu_lane = t % 64;
+            body();
+        }
+    }
+}
+
+namespace {
+
+int g_failures = 0;
+#define CHECK(c, ...)                        \
+    do {                                     \
+        if (!(c)) {                          \
+            fprintf(stderr, "FAIL: " __VA_ARGS__); \
+            fprintf(stderr, "\n");           \
+            g_failures++;                    \
+        }                                    \
+    } while (0)
+
+uint32_t g_rng = 2463534242u;
+uint32_t rnd32() {
+    g_rng = g_rng * 1664525u + 1013904223u;
+    return g_rng >> 8;
+}
+uint8_t rnd() { return (uint8_t)rnd32(); }
+
+constexpr uint8_t kCanary = 0xC3, kFill = 0x5A;
+
+// n bytes at alignment `align` (mod 16), ending where their heap block ends.
+struct Buf {
+    uint8_t* base;
+    uint8_t* p;
+    size_t align, n;
+    Buf(size_t align_, size_t n_) : align(align_ & 15), n(n_) {
+        base = static_cast<uint8_t*>(malloc(align + n));
+        if (!base) abort();
+        p = base + align;
+        memset(base, kCanary, align);
+        EMU_POISON(base, align & ~size_t(7));
+    }
+    Buf(const Buf&) = delete;
+    Buf& operator=(const Buf&) = delete;
+    ~Buf() {
+        EMU_UNPOISON(base, align & ~size_t(7));
+        free(base);
+    }
+    void fill_random() {
+        for (size_t i = 0; i < n; ++i) p[i] = rnd();
+    }
+    void fill(uint8_t v) { memset(p, v, n); }
+    bool all(uint8_t v) const {
+        for (size_t i = 0; i < n; ++i)
+            if (p[i] != v) return false;
+        return true;
+    }
+    bool canary_ok() const {
+        for (size_t i = align & ~size_t(7); i < align; ++i)
+            if (base[i] != kCanary) return false;
+        return true;
+    }
+    template <class T>
+    T* as() {
+        return reinterpret_cast<T*>(p);
+    }
+};
+typedef std::unique_ptr<Buf> BufP;
+
+// The lowest address of a set of buffers: the batch's base pointer, so that
+// every offset is a forward one.
+const uint8_t* lowest(const std::vector<BufP>& v) {
+    const uint8_t* lo = nullptr;
+    for (const BufP& b : v)
+        if (!lo || b->p < lo) lo = b->p;
+    return lo;
+}
+
+struct Entry {
+    uint32_t src_len;
+    int32_t ret;
+    uint32_t src_align, frame_align;
+};
+Entry frame_of(uint32_t len, uint32_t sa = 0, uint32_t fa = 0) {  // len >= 1
+    return Entry{len + 1 + rnd32() % 7, (int32_t)len, sa, fa};
+}
+Entry raw_of(uint32_t len, uint32_t sa = 0, uint32_t fa = 0) {
+    // a failed compress, a frame as large as the input, a larger one, a negative ret
+    const int32_t rets[4] = {0, (int32_t)len, (int32_t)len + 5, -3};
+    return Entry{len, rets[rnd32() % 4], sa, fa};
+}
+
+enum Cap { kCapExact, kCapOneShort, kCapZero };
+
+// One lz4e_pack_batch_dev against its restatement in plain C.
+void pack_case(const char* what, const std::vector<Entry>& es, uint32_t align, uint32_t packed_align, Cap cap) {
+    const uint32_t n = (uint32_t)es.size();
+    // ---- the restatement ----
+    std::vector<uint64_t> want_off(n + 1);
+    std::vector<int32_t> want_len(n);
+    std::vector<uint8_t> want_kind(n);
+    uint64_t at = 0;
+    uint32_t max_len = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const bool frame = es[i].ret > 0 && (uint32_t)es[i].ret < es[i].src_len;
+        want_kind[i] = frame ? LZ4E_PACK_FRAME : LZ4E_PACK_RAW;
+        want_len[i] = frame ? es[i].ret : (int32_t)es[i].src_len;
+        want_off[i] = at;
+        at += ((uint64_t)want_len[i] + align - 1) / align * align;
+        if (es[i].src_len > max_len) max_len = es[i].src_len;
+    }
+    want_off[n] = at;
+    const uint64_t total = at;
+    // ---- the batch: what an entry's kind does not read is 0 bytes long ----
+    std::vector<BufP> slots, srcs;
+    for (uint32_t i = 0; i < n; ++i) {
+        const bool frame = want_kind[i] == LZ4E_PACK_FRAME;
+        slots.emplace_back(new Buf(es[i].frame_align, frame ? (size_t)es[i].ret : 0));
+        srcs.emplace_back(new Buf(es[i].src_align, frame ? 0 : es[i].src_len));
+        slots[i]->fill_random();
+        srcs[i]->fill_random();
+    }
+    const uint8_t* frames = lowest(slots);
+    const uint8_t* src = lowest(srcs);
+    Buf fr_off(0, 8 * (size_t)n), src_off(0, 8 * (size_t)n), ret(0, 4 * (size_t)n), src_len(0, 4 * (size_t)n);
+    Buf pk_off(0, 8 * ((size_t)n + 1)), pk_len(0, 4 * (size_t)n), pk_kind(0, n);
+    for (uint32_t i = 0; i < n; ++i) {
+        fr_off.as<uint64_t>()[i] = (uint64_t)(slots[i]->p - frames);
+        src_off.as<uint64_t>()[i] = (uint64_t)(srcs[i]->p - src);
+        ret.as<int32_t>()[i] = es[i].ret;
+        src_len.as<uint32_t>()[i] = es[i].src_len;
+    }
+    pk_off.fill(kFill);
+    pk_len.fill(kFill);
+    pk_kind.fill(kFill);
+    std::vector<uint8_t> image(total, 0);
+    for (uint32_t i = 0; i < n; ++i)
+        if (want_len[i])
+            memcpy(image.data() + want_off[i], want_kind[i] == LZ4E_PACK_FRAME ? slots[i]->p : srcs[i]->p,
+                   (size_t)want_len[i]);
+    const uint64_t packed_cap = cap == kCapExact ? total : (cap == kCapOneShort && total ? total - 1 : 0);
+    const bool fits = total <= packed_cap;
+    Buf packed(packed_align, packed_cap);
+    packed.fill(kFill);
+    // ---- the kernels ----
+    const lz4e::PackBatch a{frames, fr_off.as<uint64_t>(), ret.as<int32_t>(), src, src_off.as<uint64_t>(),
+                            src_len.as<uint32_t>(), packed.p, packed_cap, align, pk_off.as<uint64_t>(),
+                            pk_len.as<int32_t>(), pk_kind.as<uint8_t>(), n, max_len};
+    CHECK(lz4e::launch_pack(a, nullptr) == hipSuccess, "%s: launch", what);
+    bool index_ok = memcmp(pk_off.p, want_off.data(), pk_off.n) == 0;
+    if (n) index_ok &= memcmp(pk_len.p, want_len.data(), pk_len.n) == 0 && memcmp(pk_kind.p, want_kind.data(), n) == 0;
+    CHECK(index_ok, "%s: index (n %u, align %u)", what, n, align);
+    if (fits)
+        CHECK(total == 0 || memcmp(packed.p, image.data(), total) == 0, "%s: image (n %u, align %u, packed at %u mod 16)",
+              what, n, align, packed_align);
+    else
+        CHECK(packed.all(kFill), "%s: packed written although %llu > cap %llu", what, (unsigned long long)total,
+              (unsigned long long)packed_cap);
+    bool canaries = packed.canary_ok();
+    for (uint32_t i = 0; i < n; ++i) canaries &= slots[i]->canary_ok() && srcs[i]->canary_ok();
+    CHECK(canaries, "%s: canary (n %u)", what, n);
+}
+
+struct UEntry {
+    uint8_t kind;
+    int32_t len, cap;
+    uint32_t dst_align;
+};
+
+// unpack_mask_kernel and unpack_raw_kernel on an image of the given entries
+// (align 1), `packed` at packed_align mod 16.
+void unpack_case(const char* what, const std::vector<UEntry>& es, uint32_t packed_align) {
+    const uint32_t n = (uint32_t)es.size();
+    constexpr int32_t kUntouched = -7777;
+    Buf pk_off(0, 8 * ((size_t)n + 1)), pk_len(0, 4 * (size_t)n), pk_kind(0, n), dst_off(0, 8 * (size_t)n),
+        dst_cap(0, 4 * (size_t)n), ret(0, 4 * (size_t)n), masked(0, 4 * (size_t)n);
+    uint64_t at = 0;
+    uint32_t max_cap = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        pk_off.as<uint64_t>()[i] = at;
+        at += (uint64_t)(es[i].len > 0 ? es[i].len : 0);
+        pk_len.as<int32_t>()[i] = es[i].len;
+        pk_kind.as<uint8_t>()[i] = es[i].kind;
+        dst_cap.as<int32_t>()[i] = es[i].cap;
+        ret.as<int32_t>()[i] = kUntouched;
+        if (es[i].cap > 0 && (uint32_t)es[i].cap > max_cap) max_cap = (uint32_t)es[i].cap;
+    }
+    pk_off.as<uint64_t>()[n] = at;
+    Buf packed(packed_align, at);
+    packed.fill_random();
+    std::vector<BufP> dsts;
+    for (uint32_t i = 0; i < n; ++i) {
+        dsts.emplace_back(new Buf(es[i].dst_align, es[i].cap > 0 ? (size_t)es[i].cap : 0));
+        dsts[i]->fill(kFill);
+    }
+    uint8_t* dst = const_cast<uint8_t*>(lowest(dsts));
+    for (uint32_t i = 0; i < n; ++i) dst_off.as<uint64_t>()[i] = (uint64_t)(dsts[i]->p - dst);
+    masked.fill(kFill);
+    CHECK(lz4e::launch_unpack_mask(pk_len.as<int32_t>(), pk_kind.as<uint8_t>(), n, masked.as<int32_t>(), nullptr) ==
+              hipSuccess,
+          "%s: mask launch", what);
+    const lz4e::UnpackRawBatch a{packed.p, pk_off.as<uint64_t>(), pk_len.as<int32_t>(), pk_kind.as<uint8_t>(), dst,
+                                 dst_off.as<uint64_t>(), dst_cap.as<int32_t>(), ret.as<int32_t>(), n, max_cap};
+    CHECK(lz4e::launch_unpack_raw(a, nullptr) == hipSuccess, "%s: raw launch", what);
+    for (uint32_t i = 0; i < n; ++i) {
+        const UEntry& e = es[i];
+        const int32_t m = masked.as<int32_t>()[i], r = ret.as<int32_t>()[i];
+        CHECK(m == (e.kind == LZ4E_PACK_FRAME ? e.len : 0), "%s: masked[%u] = %d (kind %u, len %d)", what, i, m, e.kind,
+              e.len);
+        const uint8_t* from = packed.p + pk_off.as<uint64_t>()[i];
+        if (e.kind == LZ4E_PACK_FRAME) {  // the decoders' entry: the raw kernel leaves it alone
+            CHECK(r == kUntouched && dsts[i]->all(kFill), "%s: frame entry %u touched (ret %d)", what, i, r);
+        } else if (e.kind == LZ4E_PACK_RAW && e.len >= 0 && e.len <= e.cap) {
+            bool good = r == e.len && (e.len == 0 || memcmp(dsts[i]->p, from, (size_t)e.len) == 0);
+            for (size_t k = (size_t)e.len; k < dsts[i]->n; ++k) good &= dsts[i]->p[k] == kFill;
+            CHECK(good, "%s: raw entry %u (len %d, cap %d, dst at %u mod 16): ret %d", what, i, e.len, e.cap,
+                  e.dst_align, r);
+        } else {
+            CHECK(r == -1 && dsts[i]->all(kFill), "%s: entry %u (kind %u, len %d, cap %d) must fail untouched: ret %d",
+                  what, i, e.kind, e.len, e.cap, r);
+        }
+        CHECK(dsts[i]->canary_ok(), "%s: bytes before destination %u written", what, i);
+    }
+    CHECK(packed.canary_ok(), "%s: packed canary", what);
+}
+
+const uint32_t kLens[] = {0, 1, 15, 16, 17, 31, 33, 511, 512, 4096, 4097, 70000};
+constexpr uint32_t kSmallLens = 7;  // 0 ... 33
+
+Entry entry_of(uint32_t len, bool frame, uint32_t sa, uint32_t fa) {
+    return frame && len ? frame_of(len, sa, fa) : raw_of(len, sa, fa);
+}
+
+}  // namespace
+
+int main() {
+    const uint32_t T = lz4e::kPackTile;
+    // ---- pack: every source residue against every packed residue, lengths up to 33 ----
+    // align 1; ahead of each entry a raw filler whose length puts it at the wanted residue
+    for (uint32_t li = 0; li < kSmallLens; ++li)
+        for (uint32_t frame = 0; frame < 2; ++frame) {
+            std::vector<Entry> es;
+            uint64_t at = 0;
+            for (uint32_t sa = 0; sa < 16; ++sa)
+                for (uint32_t da = 0; da < 16; ++da) {
+                    const uint32_t fill = (uint32_t)((da + 16 - at % 16) % 16);
+                    if (fill) es.push_back(raw_of(fill, (sa * 7 + da) & 15, da));
+                    es.push_back(entry_of(kLens[li], frame != 0, sa, sa));
+                    at += fill + kLens[li];
+                }
+            pack_case("residues", es, 1, 0, kCapExact);
+            pack_case("residues", es, 1, 5 + li, kCapExact);
+        }
+    // ---- every length, all-raw / all-frame / alternating, every align, three capacities ----
+    for (uint32_t align : {1u, 16u, 512u, 4096u})
+        for (uint32_t mix = 0; mix < 3; ++mix)
+            for (Cap cap : {kCapExact, kCapOneShort, kCapZero}) {
+                std::vector<Entry> es;
+                uint32_t k = 0;
+                for (uint32_t len : kLens) {
+                    const bool frame = mix == 1 || (mix == 2 && (k & 1));
+                    es.push_back(entry_of(len, frame, (k * 3 + align) & 15, (k * 11 + 5) & 15));
+                    ++k;
+                }
+                pack_case(mix == 0 ? "all raw" : mix == 1 ? "all frame" : "alternating", es, align, (align + mix) & 15, cap);
+            }
+    // ---- the scan: block counts around the tile, and one that takes the tile-sum workgroup round twice ----
+    for (uint32_t n : {0u, 1u, T - 1, T, T + 1, 2 * T + 1, T * 64 + 1})
+        for (uint32_t align : {1u, 512u}) {
+            if (n > 2 * T + 1 && align != 1) continue;
+            std::vector<Entry> es;
+            for (uint32_t i = 0; i < n; ++i) es.push_back(entry_of(rnd32() % 4, (i & 1) != 0, i & 15, (i >> 4) & 15));
+            pack_case("scan", es, align, n & 15, kCapExact);
+            if (n <= 2 * T + 1) pack_case("scan, no room", es, align, 0, n & 1 ? kCapOneShort : kCapZero);
+        }
+    // ---- unpack: mask and raw copy ----
+    for (uint32_t da = 0; da < 16; ++da) {
+        std::vector<UEntry> es;
+        uint32_t k = 0;
+        for (uint32_t len : kLens) {
+            const int32_t L = (int32_t)len;
+            es.push_back({LZ4E_PACK_RAW, L, L, (da + k) & 15});        // fits exactly
+            es.push_back({LZ4E_PACK_RAW, L, L + 9, (da * 3 + k) & 15});  // room to spare
+            es.push_back({LZ4E_PACK_RAW, L, L - 1, da});               // one byte short (len 0: cap -1)
+            es.push_back({LZ4E_PACK_RAW, L, 0, da});                   // no room (len 0: an empty copy)
+            es.push_back({LZ4E_PACK_FRAME, L, L + 40, da});            // the decoders' entry
+            es.push_back({2, L, L + 40, da});                          // an unknown kind
+            es.push_back({255, L, L, da});
+            ++k;
+        }
+        es.push_back({LZ4E_PACK_RAW, -5, 64, da});  // a corrupt index
+        unpack_case("unpack", es, da);
+    }
+    for (uint32_t pa = 0; pa < 16; ++pa)  // every packed residue against every destination residue
+        for (uint32_t li = 1; li < kSmallLens; ++li) {
+            std::vector<UEntry> es;
+            for (uint32_t k = 0; k < 16; ++k) es.push_back({LZ4E_PACK_RAW, (int32_t)kLens[li], (int32_t)kLens[li], k});
+            unpack_case("unpack residues", es, pa);
+        }
+    unpack_case("unpack, no entry", {}, 0);
+    if (g_failures) {
+        fprintf(stderr, "emu_pack: %d failures\n", g_failures);
+        return 1;
+    }
+    printf("emu_pack ok\n");
+    return 0;
+}
