@@ -39,7 +39,7 @@ struct DecompressBatch {
     int32_t* ret;
     uint32_t nblocks;
     // Upper bound of dst_cap[] (0: unknown); with the batch size it selects
-    // the decoder (launch_impl in lz4e_decompress.hip lists the order).
+    // the decoder (pick_decoder in lz4e_decompress.hip).
     uint32_t max_cap;
     uint32_t mode = 0;  // kDecAuto, or force kDecWave / kDecPipe / kDecSmall / kDecGroup / kDecGroupNoBail (tests, A/B)
     // Dictionary mode (nullable): block i decodes with the dict_len[i] bytes

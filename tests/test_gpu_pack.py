@@ -113,7 +113,7 @@ def test_round_trip_every_size(gpu, align):
 
 
 # One batch per rule of lz4e_decompress_batch_dev2's decoder choice
-# (csrc/lz4e_decompress.hip launch_impl), 64 distinct blocks repeated.
+# (csrc/lz4e_decompress.hip pick_decoder), 64 distinct blocks repeated.
 DECODER_BATCHES = {
     "pipelined_by_capacity": (6, 65536),   # capacity 16-128 KiB
     "group": (16384, 4096),                # <= 4608 bytes, >= 16384 blocks

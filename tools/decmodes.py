@@ -1,10 +1,10 @@
 """Diagnostic: decoder kernels side by side -- the one-wave decoder (1), the
-pipelined 4-wave decoder (2) and the chunked decoder (4) on the same frames
-(compressed on the GPU), kernel time by HIP events (median of the timed
-launches after one warm-up; outputs checked equal to the input and the
-return values to the block sizes).
+pipelined 4-wave decoder (2), the one-wave decoder's LDS form (6) and the
+group decoder (7) on the same frames (compressed on the GPU), kernel time by
+HIP events (median of the timed launches after one warm-up; outputs checked
+equal to the input and the return values to the block sizes).
 
-usage: python tools/decmodes.py [modes, e.g. 2,4] [workloads, e.g. silesia,text256k,fio4k,classes]"""
+usage: python tools/decmodes.py [modes, e.g. 1,2] [workloads, e.g. silesia,text256k,fio4k,classes]"""
 import ctypes
 import os
 import sys
@@ -82,7 +82,7 @@ def run(name, data, bs, cls, modes, reps=5):
 
 
 if __name__ == "__main__":
-    modes = [int(x) for x in (sys.argv[1] if len(sys.argv) > 1 else "2,4").split(",")]
+    modes = [int(x) for x in (sys.argv[1] if len(sys.argv) > 1 else "1,2").split(",")]
     wls = (sys.argv[2] if len(sys.argv) > 2 else "silesia,text256k,fio4k,classes").split(",")
     if "classes" in wls:
         for kind in ("text", "ints", "records", "runs", "random", "jpeg"):

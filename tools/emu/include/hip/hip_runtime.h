@@ -100,7 +100,7 @@ struct EmuWave {
     }
     EmuBarrier& group_bar(uint32_t width, uint32_t lane) {
         // groups of 2, 4, ..., 32 lanes only (a width of 1 or 64 has no
-        // barrier here: lz4e_decompress.hip's static_assert keeps kGroup in range)
+        // barrier here: kGroup is 8, lz4e_dec_group.h)
         if (width < 2 || width > 32 || (width & (width - 1)) != 0) abort();
         uint32_t base = 0;
         for (uint32_t w = 2; w < width; w *= 2) base += 64 / w;
