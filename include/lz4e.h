@@ -213,7 +213,17 @@ int lz4e_decompress_batch(const char *const *src, const int *csize,
  * stream-ordered pool: hipMallocAsync / hipFreeAsync); the bytes written
  * never depend on it.
  * Returns 0 on a successful launch, else a negative error.
+ *
+ * ret[i] == LZ4E_COMPRESS_ABORTED: a block above the LDS staging limit is
+ * compressed by two waves, a parser and a flusher that writes the frame from
+ * the parser's sequence records; every wait between them is bounded (about a
+ * second plus a term per input byte with no progress at all), and this value
+ * says that one ran out: a broken invariant of the kernel, never a property
+ * of the input.  The frame bytes are then undefined.  The value is negative,
+ * so every path that takes ret <= 0 as "did not compress" (the host entry
+ * points, lz4e_pack_batch_dev's raw fallback) handles it as such.
  */
+#define LZ4E_COMPRESS_ABORTED (-2147483647 - 1)
 int lz4e_compress_batch_dev(const uint8_t *src, const uint64_t *src_off,
 			    const uint32_t *src_len, const uint8_t *table_type,
 			    uint8_t *dst, const uint64_t *dst_off,

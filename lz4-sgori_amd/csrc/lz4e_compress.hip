@@ -33,7 +33,9 @@
 //    hold exactly the puts of the probes up to it.
 //  * A block read from HBM whose output cannot fill up does not emit from
 //    inside the parse at all: its sequences become 8-byte records, written
-//    out as frame bytes 64 at a time (deferred emit, flush_records).
+//    out as frame bytes 64 at a time (deferred emit, flush_step) -- by a
+//    second wave of the block's workgroup, so the parse never stops for it
+//    (flusher_wave).
 //
 // Stores may write up to 3 bytes past the bytes they own when a later store
 // of the same wave (program order) rewrites those bytes, and never past the
@@ -49,6 +51,7 @@
 #include "lz4e_device.h"
 #include "lz4e_gpu.h"
 #include "lz4e_order.h"
+#include "lz4e_results.h"
 
 namespace lz4e {
 
@@ -165,13 +168,14 @@ struct Stamps {
 enum { kPhSearch, kPhStripe, kPhLit, kPhCount, kPhRematch, kPhTail };
 
 // Event trace of the stamped build when compiled with -DLZ4E_TRACE (debug
-// only): (kind << 56 | a, b) pairs after the 8 stamp words of the block.
+// only): (kind << 56 | a, b) pairs after the kCompressStampWords stamp words
+// of the block (a single-block launch: the pairs run on past its slot).
 #ifdef LZ4E_TRACE
 #define LZ4E_TR(k, a, b)                                                              \
     do {                                                                              \
         if (kStamps && dbg && lane == 0 && trn < (1u << 16)) {                        \
-            dbg[8 + 2 * trn] = ((uint64_t)(k) << 56) | (uint64_t)(a);                 \
-            dbg[9 + 2 * trn] = (uint64_t)(b);                                         \
+            dbg[kCompressStampWords + 2 * trn] = ((uint64_t)(k) << 56) | (uint64_t)(a); \
+            dbg[kCompressStampWords + 1 + 2 * trn] = (uint64_t)(b);                   \
         }                                                                             \
         trn++;                                                                        \
     } while (0)
@@ -313,9 +317,10 @@ LZ4E_DEV uint64_t make_record(uint32_t off, uint32_t L, uint32_t ml) {
 }
 
 // One sequence found by the exact walk, a search or at the block's end.
-LZ4E_DEV void record_seq(gu64* rec, uint32_t& nrec, uint32_t off, uint32_t L, uint32_t ml,
+// (rmask: all ones, or R - 1 where the records are a ring, see the flusher wave)
+LZ4E_DEV void record_seq(gu64* rec, uint32_t& nrec, uint32_t rmask, uint32_t off, uint32_t L, uint32_t ml,
                          uint32_t lane) {
-    if (lane == 0) rec[nrec] = make_record(off, L, ml);
+    if (lane == 0) rec[nrec & rmask] = make_record(off, L, ml);
     nrec += 1;
 }
 
@@ -327,6 +332,64 @@ LZ4E_DEV void record_seq(gu64* rec, uint32_t& nrec, uint32_t off, uint32_t L, ui
 // (up to kShortLit) literals, exactly those bytes (whole dwords, then bytes).  Longer literal runs and
 // longer extensions go first, wave-wide and in order: a copy's spare bytes are
 // then rewritten by the bytes that belong there.
+//
+// flush_step is one such step: lane q holds record r (act: it has one).
+template <class IMG>
+LZ4E_DEV void flush_step(const IMG& img, gu8* out, uint64_t r, bool act, uint32_t& op, uint32_t& rpos,
+                         uint32_t lane) {
+    const uint32_t w0 = (uint32_t)r, w1 = (uint32_t)(r >> 32);
+    const uint32_t off = w0 & 0xFFFFu;
+    const uint32_t L = ((w0 >> 16) & 0xFFu) | ((w1 & 0xFFFFu) << 8);
+    const uint32_t ml = (w0 >> 24) | ((w1 >> 16) << 8);
+    const uint32_t mc = ml - 4;  // (ml == 0: no match part)
+    const uint32_t lx = L >= 15 ? (L - 15) / 255 + 1 : 0;
+    const uint32_t mx = ml == 0 ? 0 : 2 + (mc >= 15 ? (mc - 15) / 255 + 1 : 0);
+    const uint32_t size = act ? 1 + lx + L + mx : 0;
+    const uint32_t span = act ? L + ml : 0;
+    const uint32_t oe = wave_incl_add(size), pe = wave_incl_add(span);
+    const uint32_t o = op + oe - size;      // token
+    const uint32_t lo = o + 1 + lx;         // literals
+    const uint32_t ip = rpos + pe - span;   // their source
+    uint64_t wide = ballot(act && (L > kShortLit || lx > 1 || mx > 3));
+    while (wide) {
+        const uint32_t q = ctz64(wide);
+        wide &= wide - 1;
+        const uint32_t Lq = lane_val(L, q), mlq = lane_val(ml, q), loq = lane_val(lo, q);
+        if (Lq >= 15 + 255) out_ext(out, lane_val(o, q) + 1, Lq - 15, lane);
+        if (Lq > kShortLit) {
+            if (mlq != 0) out_copy(out, loq, img, lane_val(ip, q), Lq, lane);
+            else out_copy_exact(out, loq, img, lane_val(ip, q), Lq, lane);
+        }
+        lockstep();  // the extension overwrites the copy's spare bytes
+        if (mlq >= 4 + 15 + 255) out_ext(out, loq + Lq + 2, mlq - 4 - 15, lane);
+    }
+    lockstep();  // so do the tokens and offsets below
+    const uint32_t Ls = act && L <= kShortLit ? L : 0, whole = Ls & ~3u;
+    uint32_t tail[3], w[kShortLit / 4];  // every load first: one round trip for the step
+#pragma unroll
+    for (uint32_t j = 0; j < 3; ++j) tail[j] = whole + j < Ls ? img.rd8(ip + whole + j) : 0;
+#pragma unroll
+    for (uint32_t j = 0; j < kShortLit / 4; ++j) w[j] = 4 * j < whole ? img.ld32(ip + 4 * j) : 0;
+#pragma unroll
+    for (uint32_t j = 0; j < kShortLit / 4; ++j)
+        if (4 * j < whole) st32(out, lo + 4 * j, w[j]);
+#pragma unroll
+    for (uint32_t j = 0; j < 3; ++j)
+        if (whole + j < Ls) out[lo + whole + j] = (uint8_t)tail[j];
+    if (act) {
+        out[o] = (uint8_t)(((L < 15 ? L : 15) << 4) | (ml == 0 ? 0 : (mc < 15 ? mc : 15)));
+        if (lx == 1) out[o + 1] = (uint8_t)(L - 15);
+        if (ml != 0) {
+            out[lo + L] = (uint8_t)off;
+            out[lo + L + 1] = (uint8_t)(off >> 8);
+            if (mx == 3) out[lo + L + 2] = (uint8_t)(mc - 15);
+        }
+    }
+    op += lane_val(oe, kWave - 1);
+    rpos += lane_val(pe, kWave - 1);
+}
+
+// One wave both parses and emits: every waiting record, then nrec returns to 0.
 template <bool kStamps, class IMG>
 LZ4E_DEV void flush_records(const IMG& img, gu8* out, const gu64* rec, uint32_t& nrec, uint32_t& op,
                             uint32_t& rpos, Stamps& st, uint32_t lane) {
@@ -334,59 +397,142 @@ LZ4E_DEV void flush_records(const IMG& img, gu8* out, const gu64* rec, uint32_t&
     for (uint32_t base = 0; base < nrec; base += kWave) {
         const bool act = base + lane < nrec;
         const uint64_t r = act ? rec[base + lane] : 0;
-        const uint32_t w0 = (uint32_t)r, w1 = (uint32_t)(r >> 32);
-        const uint32_t off = w0 & 0xFFFFu;
-        const uint32_t L = ((w0 >> 16) & 0xFFu) | ((w1 & 0xFFFFu) << 8);
-        const uint32_t ml = (w0 >> 24) | ((w1 >> 16) << 8);
-        const uint32_t mc = ml - 4;  // (ml == 0: no match part)
-        const uint32_t lx = L >= 15 ? (L - 15) / 255 + 1 : 0;
-        const uint32_t mx = ml == 0 ? 0 : 2 + (mc >= 15 ? (mc - 15) / 255 + 1 : 0);
-        const uint32_t size = act ? 1 + lx + L + mx : 0;
-        const uint32_t span = act ? L + ml : 0;
-        const uint32_t oe = wave_incl_add(size), pe = wave_incl_add(span);
-        const uint32_t o = op + oe - size;      // token
-        const uint32_t lo = o + 1 + lx;         // literals
-        const uint32_t ip = rpos + pe - span;   // their source
-        uint64_t wide = ballot(act && (L > kShortLit || lx > 1 || mx > 3));
-        while (wide) {
-            const uint32_t q = ctz64(wide);
-            wide &= wide - 1;
-            const uint32_t Lq = lane_val(L, q), mlq = lane_val(ml, q), loq = lane_val(lo, q);
-            if (Lq >= 15 + 255) out_ext(out, lane_val(o, q) + 1, Lq - 15, lane);
-            if (Lq > kShortLit) {
-                if (mlq != 0) out_copy(out, loq, img, lane_val(ip, q), Lq, lane);
-                else out_copy_exact(out, loq, img, lane_val(ip, q), Lq, lane);
-            }
-            lockstep();  // the extension overwrites the copy's spare bytes
-            if (mlq >= 4 + 15 + 255) out_ext(out, loq + Lq + 2, mlq - 4 - 15, lane);
-        }
-        lockstep();  // so do the tokens and offsets below
-        const uint32_t Ls = act && L <= kShortLit ? L : 0, whole = Ls & ~3u;
-        uint32_t tail[3], w[kShortLit / 4];  // every load first: one round trip for the step
-#pragma unroll
-        for (uint32_t j = 0; j < 3; ++j) tail[j] = whole + j < Ls ? img.rd8(ip + whole + j) : 0;
-#pragma unroll
-        for (uint32_t j = 0; j < kShortLit / 4; ++j) w[j] = 4 * j < whole ? img.ld32(ip + 4 * j) : 0;
-#pragma unroll
-        for (uint32_t j = 0; j < kShortLit / 4; ++j)
-            if (4 * j < whole) st32(out, lo + 4 * j, w[j]);
-#pragma unroll
-        for (uint32_t j = 0; j < 3; ++j)
-            if (whole + j < Ls) out[lo + whole + j] = (uint8_t)tail[j];
-        if (act) {
-            out[o] = (uint8_t)(((L < 15 ? L : 15) << 4) | (ml == 0 ? 0 : (mc < 15 ? mc : 15)));
-            if (lx == 1) out[o + 1] = (uint8_t)(L - 15);
-            if (ml != 0) {
-                out[lo + L] = (uint8_t)off;
-                out[lo + L + 1] = (uint8_t)(off >> 8);
-                if (mx == 3) out[lo + L + 2] = (uint8_t)(mc - 15);
-            }
-        }
-        op += lane_val(oe, kWave - 1);
-        rpos += lane_val(pe, kWave - 1);
+        flush_step(img, out, r, act, op, rpos, lane);
     }
     nrec = 0;
     if (kStamps) st.lap(kPhTail);
+}
+
+// ---- the flusher wave ------------------------------------------------------
+// The HBM-image records kernel runs a block as two waves.  Wave 0 parses and
+// only stores records (compress_block<.., kTwo>): its record buffer is a ring
+// (slot = record number mod R), and it neither knows the frame position nor
+// stops to emit.  Wave 1 (flusher_wave) owns op and rpos and runs flush_step
+// over the records wave 0 has published, 64 a step.  The hand-over is the
+// pipelined decoder's (lz4e_dec_pipe.h): in-order counters in LDS behind the
+// table, workgroup-scope release / acquire.
+//   pub   records complete in the ring (parser -> flusher).  The release waits
+//         for the parser's record stores, so it is not made per window: at a
+//         window's start once kPubBatch records are unpublished, when the ring
+//         is short of space, and at the block's end.
+//   cons  records the flusher has in registers: their slots are free
+//         (flusher -> parser).  The parser keeps a copy and reads the counter
+//         again only when the copy leaves fewer than 64 slots free.
+//   done  the parser has published its last record; a0 / a1 hold its post-state.
+//   abort a wait ran out (see below): both waves leave.
+// Waits: the parser only for ring space (records - cons > R - 64), the flusher
+// only for pub / done.  The flusher takes a step whenever 64 records wait, and a
+// shorter one when the parser is done or more than R - 64 records wait -- which
+// a blocked parser always leaves (it publishes everything before it waits) --
+// so the two never wait for each other.
+// Every wait is bounded as the decoder's are: kCSpinMax sleeps (>= 128 cycles
+// each) plus kCSpinPerByte per input byte with the watched counter standing
+// still.  Between two moves of `pub` the parser runs at most the windows of 64
+// records and of one search, which advances at least one byte per window
+// (a window: a few thousand cycles, ~16 k under the worst contention seen), so
+// at most n windows: 128 sleeps per byte cover it; between two moves of `cons`
+// the flusher emits one step, at most n literal bytes at 2 KiB per round trip.
+// On expiry the block's ret is kCompressAborted (LZ4E_COMPRESS_ABORTED,
+// include/lz4e.h) and both waves leave.  Only a broken invariant can fire it.
+struct FlushLds {
+    uint32_t pub, cons, done, abort;
+    uint32_t a0, a1, pad[2];
+};
+constexpr uint32_t kFlushLdsBytes = sizeof(FlushLds);
+constexpr uint32_t kPubBatch = kWave;
+#ifndef LZ4E_CSPIN_MAX
+#define LZ4E_CSPIN_MAX (1u << 23)
+#endif
+#ifndef LZ4E_CSPIN_PER_BYTE
+#define LZ4E_CSPIN_PER_BYTE 128
+#endif
+constexpr uint32_t kCSpinMax = LZ4E_CSPIN_MAX, kCSpinPerByte = LZ4E_CSPIN_PER_BYTE;
+// (n < 2^24 in a deferred block: no overflow)
+LZ4E_DEV uint32_t flush_spin_max(uint32_t n) { return kCSpinMax + n * kCSpinPerByte; }
+
+LZ4E_DEV uint32_t hs_acquire(uint32_t* p) {
+    return uni(__hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
+}
+// Called by every lane of the wave (see lds_release, lz4e_dec_pipe.h).
+LZ4E_DEV void hs_release(uint32_t* p, uint32_t v) {
+    lockstep();
+    __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// The parser at a window's start with nrec records written, pubd of them
+// published: once kPubBatch are unpublished or the ring is short of space it
+// publishes them all and waits until at most rlim = R - 64 are unconsumed.
+// False: the wait ran out, or the flusher's did.
+LZ4E_DEV bool parser_hand_over(FlushLds* S, uint32_t nrec, uint32_t& pubd, uint32_t& cons, uint32_t rlim,
+                               uint32_t n) {
+    if (nrec - pubd < kPubBatch && nrec - cons <= rlim) return true;
+    if (nrec != pubd) {
+        // (a workgroup-scope release alone does not wait for global stores)
+        stores_done();
+        hs_release(&S->pub, nrec);
+        pubd = nrec;
+    }
+    if (nrec - cons <= rlim) return true;
+    const uint32_t spin_max = flush_spin_max(n);
+    for (uint32_t k = 0;; ++k) {
+        const uint32_t c = hs_acquire(&S->cons);
+        if (c != cons) {
+            cons = c;
+            k = 0;
+        }
+        if (nrec - cons <= rlim) return true;
+        if (k >= spin_max || hs_acquire(&S->abort)) {
+            hs_release(&S->abort, 1);
+            return false;
+        }
+        __builtin_amdgcn_s_sleep(2);
+    }
+}
+
+// Wave 1 of a deferring block: the frame from the published records; it
+// writes the block's results (the parser's post-state comes through S).
+template <class IMG>
+LZ4E_DEV void flusher_wave(FlushLds* S, const IMG& img, gu8* out, const gu64* rec, uint32_t nrecords,
+                           uint32_t n, uint32_t D, int32_t* retp, uint32_t* auxp, uint32_t b,
+                           uint32_t lane) {
+    const uint32_t mask = nrecords - 1, rlim = nrecords - kWave;
+    const uint32_t spin_max = flush_spin_max(n);
+    uint32_t cons = 0, op = 0, rpos = D, seen = 0;
+    for (uint32_t k = 0;; ++k) {
+        const bool done = hs_acquire(&S->done) != 0;  // before pub: done means pub is final
+        const uint32_t pub = hs_acquire(&S->pub);
+        const uint32_t avail = pub - cons;
+        if (avail >= kWave || (avail != 0 && (avail > rlim || done))) {
+            const uint32_t cnt = avail < kWave ? avail : kWave;
+            const bool act = lane < cnt;
+            const uint64_t r = act ? rec[(cons + lane) & mask] : 0;
+            cons += cnt;
+            stores_done();  // (vmcnt(0): the records are in registers)
+            hs_release(&S->cons, cons);
+            flush_step(img, out, r, act, op, rpos, lane);
+            seen = pub;
+            k = 0;
+            continue;
+        }
+        if (done) break;  // and nothing waits
+        if (pub != seen) {
+            seen = pub;
+            k = 0;
+        }
+        if (k >= spin_max || hs_acquire(&S->abort)) {
+            hs_release(&S->abort, 1);
+            if (lane == 0) retp[b] = kCompressAborted;
+            return;
+        }
+        __builtin_amdgcn_s_sleep(8);
+    }
+    if (lane == 0) {
+        retp[b] = (int32_t)op;
+        if (auxp) {
+            auxp[2 * (size_t)b] = S->a0;
+            auxp[2 * (size_t)b + 1] = S->a1;
+        }
+    }
 }
 
 // The sequences of a fast chain (compress_block): event lane l holds sequence
@@ -396,11 +542,11 @@ LZ4E_DEV void flush_records(const IMG& img, gu8* out, const gu64* rec, uint32_t&
 // sequence q's token, extension bytes and offset, window lane x its literal
 // byte (lz4e_compress.c:352-453).
 template <bool kDefer>
-LZ4E_DEV void chain_out(gu8* out, uint32_t& op, gu64* rec, uint32_t& nrec, uint64_t evm, uint32_t nev,
-                        uint32_t fe, uint32_t d0, uint64_t lanes_below, uint32_t lane) {
+LZ4E_DEV void chain_out(gu8* out, uint32_t& op, gu64* rec, uint32_t& nrec, uint32_t rmask, uint64_t evm,
+                        uint32_t nev, uint32_t fe, uint32_t d0, uint64_t lanes_below, uint32_t lane) {
     const bool isev = (evm >> lane) & 1;
     if constexpr (kDefer) {
-        if (isev) rec[nrec + popc64(evm & lanes_below)] = fe;
+        if (isev) rec[(nrec + popc64(evm & lanes_below)) & rmask] = fe;
         nrec += nev;
     } else {
         // ev: lane q < nev holds the lane of event q
@@ -531,6 +677,7 @@ LZ4E_DEV uint64_t lane_range(uint32_t a, uint32_t b) {
 struct CResult {
     int32_t ret = 0;
     uint32_t a0 = 0, a1 = 0;
+    bool handed = false;  // the flusher wave writes the block's results
 };
 // Probes done (of a search that missed through its window) from which the
 // generic search takes over (LZ4E_GENERIC_FROM, experiments; 64: only for
@@ -542,11 +689,17 @@ constexpr uint32_t kGenericFrom = LZ4E_GENERIC_FROM;
 
 // kDefer (the kernel picks it per block): the output is unlimited and the
 // sequences go to the block's records rec[0 .. rlim + 64) (deferred emit).
-template <int TT, bool kStamps, bool kDefer, class IMG>
+// kTwo (with kDefer): this wave is the parser of a two-wave block -- the
+// records are a ring and the flusher wave emits them (see flusher_wave).
+template <int TT, bool kStamps, bool kDefer, bool kTwo, class IMG>
 LZ4E_DEV CResult compress_block(const IMG& img, uint32_t* smem, uint32_t n, gu8* out, uint32_t cap,
                                 uint64_t* dbg, uint32_t lane, uint32_t D, bool progress_prio, gu64* rec,
                                 uint32_t rlim) {
+    static_assert(kDefer || !kTwo, "the flusher wave emits records");
     CResult res;
+    const uint32_t rmask = kTwo ? rlim + (kWave - 1) : ~0u;
+    [[maybe_unused]] FlushLds* const S = reinterpret_cast<FlushLds*>(smem + kTableBytes / 4);
+    [[maybe_unused]] uint32_t pubd = 0, cons = 0;  // kTwo: records published, records consumed (a copy)
     // Dictionary mode (D > 0): the image is [D dictionary bytes | the n-byte
     // block], the parse starts at D and the table was preloaded from the
     // dictionary; positions are image positions throughout.
@@ -633,7 +786,11 @@ LZ4E_DEV CResult compress_block(const IMG& img, uint32_t* smem, uint32_t n, gu8*
         };
         for (;;) {
             // ================= window setup =================================
-            if constexpr (kDefer) if (nrec > rlim) flush_records<kStamps>(img, out, rec, nrec, op, rpos, st, lane);
+            // (kTwo: nrec counts every record of the block; false: a wait ran out)
+            if constexpr (kTwo)
+                if (!parser_hand_over(S, nrec, pubd, cons, rlim, n)) goto fail;
+            if constexpr (kDefer && !kTwo)
+                if (nrec > rlim) flush_records<kStamps>(img, out, rec, nrec, op, rpos, st, lane);
             if (e >= prio_next) {
                 const uint32_t q = (uint32_t)(((uint64_t)(e - D) * 4) / n);
                 prio_next = q >= 4 ? ~0u : D + (uint32_t)(((uint64_t)(q + 1) * n + 3) / 4);
@@ -895,7 +1052,7 @@ LZ4E_DEV CResult compress_block(const IMG& img, uint32_t* smem, uint32_t n, gu8*
                     }
                     if (kStamps) st.lap(kPhLit);
                     if (nev) {  // the chain's nev sequences, recorded or emitted at once
-                        chain_out<kDefer>(out, op, rec, nrec, evm, nev, fe, d0, lanes_below, lane);
+                        chain_out<kDefer>(out, op, rec, nrec, rmask, evm, nev, fe, d0, lanes_below, lane);
                         e = B + k;
                         anchor = e;
                         if (kStamps) { st.cnt[1] += nev; st.cnt[3] += nev << 16; st.lap(kPhTail); }
@@ -939,7 +1096,7 @@ LZ4E_DEV CResult compress_block(const IMG& img, uint32_t* smem, uint32_t n, gu8*
                     uint32_t t = m & ~kLong;
                     if (m & kLong) t = count_from(img, e, c, kFwd, matchlimit, lane);
                     LZ4E_TR(2, e, ((uint64_t)c << 32) | t);
-                    if constexpr (kDefer) record_seq(rec, nrec, e - c, 0, t, lane);
+                    if constexpr (kDefer) record_seq(rec, nrec, rmask, e - c, 0, t, lane);
                     else if (!emit_match(op++, 0, e - c, t - 4)) goto fail;
                     if (kStamps) st.cnt[1]++;
                     e += t;
@@ -1033,7 +1190,7 @@ LZ4E_DEV CResult compress_block(const IMG& img, uint32_t* smem, uint32_t n, gu8*
                 // literals [anchor, ipm) (lz4e_compress.c:352-382)
                 const uint32_t L = ipm - anchor;
                 if constexpr (kDefer) {
-                    record_seq(rec, nrec, ipm - cand, L, t, lane);
+                    record_seq(rec, nrec, rmask, ipm - cand, L, t, lane);
                 } else {
                     const uint32_t tok = op++;
                     if ((uint64_t)op + L + 8 + L / 255 > capl) goto fail;
@@ -1174,7 +1331,7 @@ LZ4E_DEV CResult compress_block(const IMG& img, uint32_t* smem, uint32_t n, gu8*
                 LZ4E_TR(2, ipm, ((uint64_t)cand << 32) | t);
                 const uint32_t L = ipm - anchor;
                 if constexpr (kDefer) {
-                    record_seq(rec, nrec, ipm - cand, L, t, lane);
+                    record_seq(rec, nrec, rmask, ipm - cand, L, t, lane);
                 } else {
                     const uint32_t tok = op++;
                     if ((uint64_t)op + L + 8 + L / 255 > capl) goto fail;
@@ -1205,8 +1362,18 @@ LZ4E_DEV CResult compress_block(const IMG& img, uint32_t* smem, uint32_t n, gu8*
 last_literals: {
         // lz4e_compress.c:500-530
         const uint32_t R = D + n - anchor;
-        if constexpr (kDefer) {
-            record_seq(rec, nrec, 0, R, 0, lane);
+        if constexpr (kTwo) {
+            // room for one record: at most rlim + 63 are unconsumed here
+            record_seq(rec, nrec, rmask, 0, R, 0, lane);
+            if (lane == 0) S->a0 = ip - D;
+            if (lane == 0) S->a1 = R;
+            stores_done();
+            hs_release(&S->pub, nrec);
+            hs_release(&S->done, 1);
+            res.handed = true;
+            return res;
+        } else if constexpr (kDefer) {
+            record_seq(rec, nrec, rmask, 0, R, 0, lane);
             flush_records<kStamps>(img, out, rec, nrec, op, rpos, st, lane);
         } else {
             if ((uint64_t)op + R + 1 + (R + 240) / 255 > capl) goto fail;
@@ -1238,7 +1405,10 @@ last_literals: {
         return res;
     }
 fail:
-    return res;  // 0, 0, 0
+    // 0, 0, 0: the output is full -- a two-wave block's output cannot fill up,
+    // only a hand-over wait that ran out leads here
+    res.ret = kTwo ? kCompressAborted : 0;
+    return res;
 }
 
 // Stage a block into LDS as a word image, the bytes of the last partial word
@@ -1270,30 +1440,31 @@ LZ4E_DEV void stage_block(uint32_t* dstw, const uint8_t* src, uint32_t n, uint32
     }
 }
 
-template <bool kStamps, bool kDefer, class IMG>
+template <bool kStamps, bool kDefer, bool kTwo, class IMG>
 LZ4E_DEV CResult dispatch_class(const IMG& img, uint32_t* smem, uint32_t n, int tt, gu8* out,
                                 uint32_t cap, uint64_t* dbg, uint32_t lane, uint32_t D, bool pp,
                                 gu64* rec, uint32_t rlim) {
     if (tt == kByU32)
-        return compress_block<kByU32, kStamps, kDefer>(img, smem, n, out, cap, dbg, lane, D, pp, rec, rlim);
+        return compress_block<kByU32, kStamps, kDefer, kTwo>(img, smem, n, out, cap, dbg, lane, D, pp, rec, rlim);
     if (tt == kByU16)
-        return compress_block<kByU16, kStamps, kDefer>(img, smem, n, out, cap, dbg, lane, 0, pp, rec, rlim);
-    return compress_block<kByU64, kStamps, kDefer>(img, smem, n, out, cap, dbg, lane, 0, pp, rec, rlim);
+        return compress_block<kByU16, kStamps, kDefer, kTwo>(img, smem, n, out, cap, dbg, lane, 0, pp, rec, rlim);
+    return compress_block<kByU64, kStamps, kDefer, kTwo>(img, smem, n, out, cap, dbg, lane, 0, pp, rec, rlim);
 }
 
 // Deferred emit (flush_records) where the kernel is built for it (kRecords),
 // the launch has a record buffer and the block's output is unlimited.
-template <bool kStamps, bool kRecords, class IMG>
+// kTwo: as wave 0 of a two-wave workgroup (the flusher wave takes the same decision).
+template <bool kStamps, bool kRecords, bool kTwo, class IMG>
 LZ4E_DEV CResult dispatch_emit(const IMG& img, uint32_t* smem, uint32_t n, int tt, gu8* out,
                                uint32_t cap, uint64_t* dbg, uint32_t lane, uint32_t D, bool pp,
                                uint64_t* records, uint32_t nrecords, uint32_t b) {
     if constexpr (kRecords) {
         const uint64_t bound = (uint64_t)n + n / 255 + 16;
         if (records != nullptr && cap >= bound && n < (1u << kRecLenBits))
-            return dispatch_class<kStamps, true>(img, smem, n, tt, out, cap, dbg, lane, D, pp,
+            return dispatch_class<kStamps, true, kTwo>(img, smem, n, tt, out, cap, dbg, lane, D, pp,
                                                  (gu64*)(records + (size_t)b * nrecords), nrecords - kWave);
     }
-    return dispatch_class<kStamps, false>(img, smem, n, tt, out, cap, dbg, lane, D, pp, nullptr, 0);
+    return dispatch_class<kStamps, false, false>(img, smem, n, tt, out, cap, dbg, lane, D, pp, nullptr, 0);
 }
 
 // The kernel's explicit arguments as laid out in the kernarg segment
@@ -1327,8 +1498,14 @@ static_assert(offsetof(CompressArgs, ret) == 56 && offsetof(CompressArgs, order)
 // records: the launch's record buffer, nrecords (a power of two, >= 64) slots
 // per block, or null (every block emits inline); kRecords: built with the
 // deferred emit.
+// The HBM-image kernel built with records runs two waves per block (parser and
+// flusher, see flusher_wave); the stamped build keeps the one-wave flush, so
+// that a block's stamps stay one wave's cycles.
 template <bool kLdsInput, bool kStamps, bool kRecords>
-__global__ __launch_bounds__(64) void compress_kernel(const uint8_t* __restrict__ src,
+constexpr bool kTwoWave = !kLdsInput && kRecords && !kStamps;
+
+template <bool kLdsInput, bool kStamps, bool kRecords>
+__global__ __launch_bounds__((kTwoWave<kLdsInput, kStamps, kRecords> ? 2 : 1) * kWave) void compress_kernel(const uint8_t* __restrict__ src,
                                                       const uint64_t* __restrict__ src_off,
                                                       const uint32_t* __restrict__ src_len,
                                                       const uint8_t* __restrict__ table_type,
@@ -1343,6 +1520,10 @@ __global__ __launch_bounds__(64) void compress_kernel(const uint8_t* __restrict_
                                                       uint64_t* records, uint32_t nrecords) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     if (blockIdx.x >= nblocks) return;
+    constexpr bool kTwo = kTwoWave<kLdsInput, kStamps, kRecords>;
+    constexpr uint32_t kThreads = (kTwo ? 2 : 1) * kWave;
+    // Every early return and every block_sync below is taken by both waves.
+    const uint32_t wave = kTwo ? uni(threadIdx.x / kWave) : 0;
     const uint32_t b = order ? order[blockIdx.x] : blockIdx.x;
     const uint32_t lane = lane_id();
     const uint32_t n = src_len[b];
@@ -1364,7 +1545,7 @@ __global__ __launch_bounds__(64) void compress_kernel(const uint8_t* __restrict_
         // Input too large (lz4e_compress.c:245-248) returns 0; a malformed
         // descriptor (class/length the SG rules cannot produce, or a block
         // longer than the batch's max_len) returns -1.
-        if (lane == 0) ret[b] = n > kMaxInput ? 0 : -1;
+        if (lane == 0 && wave == 0) ret[b] = n > kMaxInput ? 0 : -1;
         return;
     }
 
@@ -1372,7 +1553,11 @@ __global__ __launch_bounds__(64) void compress_kernel(const uint8_t* __restrict_
     if (n >= kMinLength) {
         // memset of the state (lz4e_compress.c:548): 16 KiB of table.
         uint4* t4 = reinterpret_cast<uint4*>(smem);
-        for (uint32_t i = lane; i < kTableBytes / 16; i += kWave) t4[i] = make_uint4(0, 0, 0, 0);
+        for (uint32_t i = wave * kWave + lane; i < kTableBytes / 16; i += kThreads) t4[i] = make_uint4(0, 0, 0, 0);
+    }
+    if constexpr (kTwo) {
+        // pub, cons, done, abort
+        if (wave == 1 && lane < 4) smem[kTableBytes / 4 + lane] = 0;
     }
 
     if constexpr (kLdsInput) {
@@ -1380,7 +1565,7 @@ __global__ __launch_bounds__(64) void compress_kernel(const uint8_t* __restrict_
         stage_block(inw, in, n, lane);
         block_sync();
         const LdsImage img{inw, n == 0 ? 0 : (n - 1) >> 2};
-        res = dispatch_emit<kStamps, kRecords>(img, smem, n, tt, out, cap, dbg_slot, lane, 0, true, records,
+        res = dispatch_emit<kStamps, kRecords, false>(img, smem, n, tt, out, cap, dbg_slot, lane, 0, true, records,
                                                nrecords, b);
     } else {
         block_sync();
@@ -1390,9 +1575,22 @@ __global__ __launch_bounds__(64) void compress_kernel(const uint8_t* __restrict_
             // LZ4_loadDict: every third dictionary position p with p + 8 <= D
             // (HASH_UNIT), in order -- the last put of a hash wins, so the
             // largest p of each hash (LDS atomic max)
-            for (uint32_t p = 3 * lane; p + 8 <= D; p += 3 * kWave)
-                atomicMax(&smem[hash_val<kByU32>(img.ld64(p))], p);
+            if (wave == 0)
+                for (uint32_t p = 3 * lane; p + 8 <= D; p += 3 * kWave)
+                    atomicMax(&smem[hash_val<kByU32>(img.ld64(p))], p);
             block_sync();
+        }
+        if constexpr (kTwo) {
+            if (wave == 1) {
+                // the flusher of a block that defers (dispatch_emit's rule);
+                // any other block emits inline on wave 0
+                const uint64_t bound = (uint64_t)n + n / 255 + 16;
+                if (records != nullptr && cap >= bound && n < (1u << kRecLenBits))
+                    flusher_wave((FlushLds*)(smem + kTableBytes / 4), img, out,
+                                 (const gu64*)(records + (size_t)b * nrecords), nrecords, n, D, ret, aux, b,
+                                 lane);
+                return;
+            }
         }
         // Issue priority: the waves furthest behind first (progress
         // priority, 3 -> 0 by quarter of the block), except in a batch that
@@ -1405,12 +1603,13 @@ __global__ __launch_bounds__(64) void compress_kernel(const uint8_t* __restrict_
             const uint32_t nh = order[nblocks];
             if (nh < nblocks - nblocks / 16) {
                 pp = false;
-                if (blockIdx.x < nh) __builtin_amdgcn_s_setprio(3);
+                if (blockIdx.x < nh) __builtin_amdgcn_s_setprio(3);  // (the parser; the flusher has left)
             }
         }
-        res = dispatch_emit<kStamps, kRecords>(img, smem, n, tt, out, cap, dbg_slot, lane, D, pp, records,
+        res = dispatch_emit<kStamps, kRecords, kTwo>(img, smem, n, tt, out, cap, dbg_slot, lane, D, pp, records,
                                                nrecords, b);
     }
+    if (res.handed) return;  // the flusher wave writes them
     // results, through pointers reloaded now (see CompressArgs)
 #ifndef LZ4E_EMU
     const __attribute__((address_space(4))) CompressArgs* ka =
@@ -1625,7 +1824,9 @@ hipError_t launch_compress_impl(const CompressBatch& a, hipStream_t stream, uint
     static const uint32_t lds_max = env_u32("LZ4E_COMPRESS_LDS_MAX", kMaxLdsInput);
     const bool lds_input = a.max_len <= lds_max && a.dict_len == nullptr;
     const dim3 grid(a.nblocks), block(kWave);
-    const uint32_t lds = compress_lds_bytes(a.max_len, lds_input);
+    uint32_t lds = compress_lds_bytes(a.max_len, lds_input);
+    constexpr bool kTwo = kTwoWave<false, kStamps, true>;
+    if (kTwo && !lds_input) lds += kFlushLdsBytes;
     // heavy blocks first (see weight_kernel)
     const int om = launch_order_mode(true);
     const bool use_order = !lds_input && (om == kOrderAlways || (om == kOrderAuto && a.nblocks >= kOrderMinBlocks &&
@@ -1655,7 +1856,7 @@ hipError_t launch_compress_impl(const CompressBatch& a, hipStream_t stream, uint
                                CompressWeight{scratch}, a.nblocks, scratch + a.nblocks, kHeavyBucket,
                                scratch + 2 * (size_t)a.nblocks);
         }
-        hipLaunchKernelGGL((compress_kernel<false, kStamps, true>), grid, block, lds, stream, a.src,
+        hipLaunchKernelGGL((compress_kernel<false, kStamps, true>), grid, dim3((kTwo ? 2 : 1) * kWave), lds, stream, a.src,
                            a.src_off, a.src_len, a.table_type, a.dst, a.dst_off, a.dst_cap, a.ret,
                            a.aux, a.nblocks, a.max_len, dbg, a.dict_len,
                            scratch ? (const uint32_t*)(scratch + a.nblocks) : nullptr, records, nrec);

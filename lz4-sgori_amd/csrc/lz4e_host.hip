@@ -34,6 +34,7 @@
 #include "lz4e_results.h"
 
 static_assert(lz4e::kDecodeAborted == LZ4E_DECODE_ABORTED, "watchdog return value");
+static_assert(lz4e::kCompressAborted == LZ4E_COMPRESS_ABORTED, "compress hand-over return value");
 
 namespace {
 

@@ -24,11 +24,14 @@ dst = torch.zeros(cap + 64, dtype=torch.uint8, device=dev)
 t = lambda a, dt: torch.tensor(a, dtype=dt, device=dev)
 offs, lens, tt, doffs, caps = t([0], torch.int64), t([n], torch.int32), t([cls], torch.uint8), t([0], torch.int64), t([cap], torch.int32)
 ret = t([-7], torch.int32)
-dbg = torch.zeros(8 + 2 * (1 << 16), dtype=torch.int64, device=dev)
+# The trace follows the block's kCompressStampWords stamp words (csrc/lz4e_gpu.h).
+CW = 16
+slot = torch.zeros(CW + 2 * (1 << 16), dtype=torch.int64, device=dev)
 rc = L.lz4e_debug_compress_stamped(src.data_ptr(), offs.data_ptr(), lens.data_ptr(), tt.data_ptr(), dst.data_ptr(),
-                                   doffs.data_ptr(), caps.data_ptr(), ret.data_ptr(), 1, n, None, dbg.data_ptr())
+                                   doffs.data_ptr(), caps.data_ptr(), ret.data_ptr(), 1, n, None, slot.data_ptr())
 torch.cuda.synchronize()
 print("rc", rc, "ret", int(ret[0]))
+dbg = slot[CW - 8:]  # the pairs start at its word 8
 dbg.cpu().numpy()[8:].tofile(os.path.join(REPO, "gpurun_out", "dbg", name + ".trace"))
 frame = dst[: int(ret[0])].cpu().numpy().tobytes()
 open(os.path.join(REPO, "gpurun_out", "dbg", name + ".tracegpu"), "wb").write(frame)

@@ -22,6 +22,9 @@ alignas(16) uint32_t smem[(16384 + 65536 + 64) / 4];
 // size here, and under LZ4E_EMU the LDS-image kernel gets one as well:
 // unlimited blocks of any size record and flush by default
 // (LZ4E_COMPRESS_RECORDS / emu_main --ring N sets the slots per block, 0 none).
+// The HBM-image kernel (blocks above the staging limit, a dictionary, or
+// emu_main --hbm) runs as its two waves, parser and flusher: 128 threads that
+// meet through the hand-over counters in the emulated LDS.
 namespace lz4e {
 int launch_order_mode(bool) { return kOrderNever; }
 }  // namespace lz4e

@@ -25,6 +25,10 @@
 // A leading "--ring N" gives the compressor N record slots per block for its
 // deferred emit (LZ4E_COMPRESS_RECORDS; 0: none, every block emits inline;
 // default: the library's).
+// A leading "--hbm" compresses through the HBM-image kernel whatever the
+// block's size (the batch's max_len is then one byte above the 4 096-byte
+// staging limit at least): two waves per block, a parser and a flusher, for
+// every block that defers its emit.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -45,6 +49,7 @@
 
 static unsigned g_src_skew = 0, g_dst_skew = 0;
 static bool g_skewed = false;  // without --skew the buffers start at the heap block's start
+static bool g_hbm = false;     // --hbm
 
 // `size` bytes whose byte `lead` sits `skew` bytes past a 16-byte boundary.
 // The heap block ends at the region's end (input: rounded up to the aligned
@@ -141,7 +146,15 @@ static int decode_main(int argc, char** argv) {
 
 int main(int argc, char** argv) {
     long cap_arg = -1;
-    while (argc > 2 && (!strcmp(argv[1], "--skew") || !strcmp(argv[1], "--cap") || !strcmp(argv[1], "--ring"))) {
+    while (argc > 2 && (!strcmp(argv[1], "--skew") || !strcmp(argv[1], "--cap") || !strcmp(argv[1], "--ring") ||
+                        !strcmp(argv[1], "--hbm"))) {
+        if (!strcmp(argv[1], "--hbm")) {
+            g_hbm = true;
+            argv[1] = argv[0];
+            argv += 1;
+            argc -= 1;
+            continue;
+        }
         if (!strcmp(argv[1], "--ring")) {
             char* end = nullptr;
             const long ring = strtol(argv[2], &end, 10);
@@ -164,7 +177,7 @@ int main(int argc, char** argv) {
         (argv[1][1] == 'd' || argv[1][1] == 'p' || argv[1][1] == 'l' || argv[1][1] == 'g' || argv[1][1] == 'G'))
         return decode_main(argc, argv);
     if (argc < 3) {
-        fprintf(stderr, "usage: emu_main [--skew S,D] [--cap N] [--ring N] BLOCK_FILE TABLE_CLASS [FRAME_OUT [DICT_FILE]]\n");
+        fprintf(stderr, "usage: emu_main [--skew S,D] [--cap N] [--ring N] [--hbm] BLOCK_FILE TABLE_CLASS [FRAME_OUT [DICT_FILE]]\n");
         return 2;
     }
     FILE* f = fopen(argv[1], "rb");
@@ -185,10 +198,11 @@ int main(int argc, char** argv) {
     const uint64_t so = D, doff = 0;
     int32_t ret = -7;
     uint32_t aux[2] = {0, 0};
+    const uint32_t max_len = g_hbm && n < 4097 ? 4097 : n;
     if (argc > 4)
-        emu_compress_batch_dict(src.p, &so, &n, &tt, dst.p, &doff, &cap, &ret, aux, 1, n, &D);
+        emu_compress_batch_dict(src.p, &so, &n, &tt, dst.p, &doff, &cap, &ret, aux, 1, max_len, &D);
     else
-        emu_compress_batch(src.p, &so, &n, &tt, dst.p, &doff, &cap, &ret, aux, 1, n);
+        emu_compress_batch(src.p, &so, &n, &tt, dst.p, &doff, &cap, &ret, aux, 1, max_len);
     if (!dst.ok() || !src.ok()) {
         fprintf(stderr, "emu_main: a store in front of a buffer\n");
         return 3;
