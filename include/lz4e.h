@@ -514,6 +514,77 @@ int lz4e_unpack_batch_dev(const uint8_t *packed, const uint64_t *pk_off,
 			  const int32_t *dst_cap, int32_t *ret, uint32_t nblocks,
 			  uint32_t max_cap, void *stream);
 
+/*
+ * Packed frame store: integrity.
+ *
+ * A checksum column for the index, computed on the device where the image
+ * is produced, and an unpack that checks every entry against it before a
+ * decoder or a copy sees the entry.  The checksum is CRC-32C (Castagnoli),
+ * the one of the Linux block layer, btrfs, iSCSI and SPDK: reflected,
+ * polynomial 0x1EDC6F41 (reversed 0x82F63B78), initial value 0xFFFFFFFF,
+ * final xor 0xFFFFFFFF; the CRC of the empty string is 0 and that of
+ * "123456789" is 0xE3069283.
+ *
+ * All pointers are device pointers.  Like pack and unpack the three calls
+ * only launch work on `stream` and are legal under stream capture: no
+ * synchronise, no host read of device data, no hipMalloc / hipFree /
+ * hipMemcpy; scratch (one word per workgroup of an entry that spans several,
+ * and the verified unpack's 9 bytes per block) comes from the stream-ordered
+ * pool.  They return 0 on a successful launch and -1 on a HIP failure, with
+ * lz4e_last_error() set.
+ *
+ * lz4e_crc32c_batch_dev: crc[i] = CRC-32C of the len[i] bytes at
+ * data + off[i]; len[i] <= 0 reads nothing and gives 0 (len[i] <=
+ * LZ4E_MAX_INPUT_SIZE).  off[] needs no alignment.  Reads stay inside
+ * [data + off[i], + len[i]) exactly (not rounded to words).  Only
+ * crc[0, nblocks) is written.  max_len is a sizing hint (it picks the
+ * threads per entry): results never depend on it, too small or too large, a
+ * wrong hint only costs time.  nblocks == 0: nothing happens.
+ *
+ * lz4e_pack_crc_batch_dev: the index's checksum column, after
+ * lz4e_pack_batch_dev on the same stream.  pk_crc[i] = CRC-32C of entry i's
+ * stored bytes, read from where pack read them (frames + fr_off[i] for
+ * LZ4E_PACK_FRAME, src + src_off[i] for LZ4E_PACK_RAW, pk_len[i] bytes; the
+ * padding is not covered).  Like the rest of the index it is written whatever
+ * packed_cap was: `packed` itself is never read, so an image that did not
+ * fit still gets its column.  Same read bounds as pack: a raw block's frame
+ * slot and a frame block's source are not read.  max_len as for pack (a
+ * hint here).  The column equals lz4e_crc32c_batch_dev(packed, pk_off,
+ * pk_len) on an image that was written.
+ *
+ * lz4e_unpack_verified_batch_dev: lz4e_unpack_batch_dev that checks each
+ * entry first.  Per entry i, in this order:
+ *   1. pk_kind[i] is neither LZ4E_PACK_FRAME nor LZ4E_PACK_RAW, or
+ *      pk_len[i] < 0: ret[i] = -1, nothing is written and the entry's bytes
+ *      are not read (its length and offset are not to be trusted).
+ *   2. the CRC-32C of packed[pk_off[i], + pk_len[i]) differs from pk_crc[i]:
+ *      ret[i] = LZ4E_UNPACK_BAD_CRC, no byte of its destination is written
+ *      and no decoder sees the entry.
+ *   3. otherwise ret[i] and the destination bytes are exactly those of
+ *      lz4e_unpack_batch_dev: decoder choice, LZ4E_DECOMPRESS_MODE, error
+ *      codes, a raw entry larger than its capacity (-1).
+ * LZ4E_UNPACK_BAD_CRC collides with no other value of ret[i]: a genuine
+ * decode error is -(ip - src) - 1 >= -0x7E000001 (the input is at most
+ * LZ4E_MAX_INPUT_SIZE bytes), and LZ4E_DECODE_ABORTED is INT32_MIN.
+ * max_cap bounds dst_cap[] (0 = unknown) as for unpack and also sizes the
+ * checksum's teams (a hint there).
+ */
+#define LZ4E_UNPACK_BAD_CRC (-2147483647)   /* INT32_MIN + 1 */
+int lz4e_crc32c_batch_dev(const uint8_t *data, const uint64_t *off,
+			  const int32_t *len, uint32_t *crc,
+			  uint32_t nblocks, uint32_t max_len, void *stream);
+int lz4e_pack_crc_batch_dev(const uint8_t *frames, const uint64_t *fr_off,
+			    const uint8_t *src, const uint64_t *src_off,
+			    const int32_t *pk_len, const uint8_t *pk_kind,
+			    uint32_t *pk_crc, uint32_t nblocks,
+			    uint32_t max_len, void *stream);
+int lz4e_unpack_verified_batch_dev(const uint8_t *packed, const uint64_t *pk_off,
+				   const int32_t *pk_len, const uint8_t *pk_kind,
+				   const uint32_t *pk_crc, uint8_t *dst,
+				   const uint64_t *dst_off, const int32_t *dst_cap,
+				   int32_t *ret, uint32_t nblocks,
+				   uint32_t max_cap, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -157,4 +157,41 @@ struct UnpackRawBatch {
 };
 hipError_t launch_unpack_raw(const UnpackRawBatch& a, hipStream_t stream);
 
+// CRC-32C of every entry of a batch (lz4e_crc.hip; include/lz4e.h
+// lz4e_crc32c_batch_dev, lz4e_pack_crc_batch_dev,
+// lz4e_unpack_verified_batch_dev).  Entry i is the len[i] bytes at
+// data + off[i]; with kinds given, a kPackRaw entry's bytes are at
+// raw + raw_off[i] instead and an entry of any other kind than these two is
+// not read.  len[i] <= 0: not read either.  crc[i] = 0 for an entry that is
+// not read.
+struct CrcBatch {
+    const uint8_t* data;
+    const uint64_t* off;
+    const uint8_t* raw;       // used with kinds only
+    const uint64_t* raw_off;
+    const uint8_t* kind;      // nullable: every entry is at data + off[i]
+    const int32_t* len;
+    uint32_t* crc;
+    uint32_t nblocks;
+    uint32_t max_len;  // sizing hint: threads per entry (no result depends on it)
+};
+// Threads per entry = 1 << crc_team_shift (16 ... 16384).  Above 256 an entry
+// spans workgroups, each leaves one partial word and a second launch combines
+// them: crc_partial_words() words of scratch (0: none needed).
+uint32_t crc_team_shift(uint32_t max_len, uint32_t nblocks);
+uint64_t crc_partial_words(uint32_t max_len, uint32_t nblocks);
+hipError_t launch_crc(const CrcBatch& a, uint32_t* partial, hipStream_t stream);
+// The verified unpack is lz4e_unpack_batch_dev's composition with two more
+// kernels.  Before the decoders: masked[i] as launch_unpack_mask's, but 0 for
+// an entry that is invalid (unknown kind, negative length) or whose checksum
+// got[i] differs from pk_crc[i]; shown[i] = pk_kind[i], kVerifyInvalid or
+// kVerifyBadCrc is the kind launch_unpack_raw is shown, which copies nothing
+// for the two markers.  After it: ret of the marked entries.
+constexpr uint32_t kVerifyInvalid = 2, kVerifyBadCrc = 3;
+constexpr int32_t kUnpackBadCrc = -2147483647;  // LZ4E_UNPACK_BAD_CRC
+hipError_t launch_unpack_verify_mask(const int32_t* pk_len, const uint8_t* pk_kind, const uint32_t* pk_crc,
+                                     const uint32_t* got, uint32_t nblocks, int32_t* masked, uint8_t* shown,
+                                     hipStream_t stream);
+hipError_t launch_unpack_verify_ret(const uint8_t* shown, uint32_t nblocks, int32_t* ret, hipStream_t stream);
+
 }  // namespace lz4e

@@ -999,6 +999,66 @@ int lz4e_unpack_batch_dev(const uint8_t* packed, const uint64_t* pk_off, const i
     return ok ? 0 : -1;
 }
 
+// The store's checksums (lz4e_crc.hip).  Launches only; the partial words of
+// entries that span workgroups come from the stream-ordered pool.
+static int crc_batch(const lz4e::CrcBatch& a, hipStream_t s, const char* what) {
+    if (a.nblocks == 0) return 0;
+    const uint64_t words = lz4e::crc_partial_words(a.max_len, a.nblocks);
+    uint32_t* partial = nullptr;
+    if (words && !hip_ok(hipMallocAsync((void**)&partial, sizeof(uint32_t) * (size_t)words, s), what)) return -1;
+    const bool ok = hip_ok(lz4e::launch_crc(a, partial, s), what);
+    if (partial) (void)hipFreeAsync(partial, s);
+    return ok ? 0 : -1;
+}
+
+int lz4e_crc32c_batch_dev(const uint8_t* data, const uint64_t* off, const int32_t* len, uint32_t* crc,
+                          uint32_t nblocks, uint32_t max_len, void* stream) {
+    g_err.clear();
+    const lz4e::CrcBatch a{data, off, nullptr, nullptr, nullptr, len, crc, nblocks, max_len};
+    return crc_batch(a, static_cast<hipStream_t>(stream), "crc32c launch");
+}
+
+int lz4e_pack_crc_batch_dev(const uint8_t* frames, const uint64_t* fr_off, const uint8_t* src,
+                            const uint64_t* src_off, const int32_t* pk_len, const uint8_t* pk_kind,
+                            uint32_t* pk_crc, uint32_t nblocks, uint32_t max_len, void* stream) {
+    g_err.clear();
+    const lz4e::CrcBatch a{frames, fr_off, src, src_off, pk_kind, pk_len, pk_crc, nblocks, max_len};
+    return crc_batch(a, static_cast<hipStream_t>(stream), "pack crc launch");
+}
+
+int lz4e_unpack_verified_batch_dev(const uint8_t* packed, const uint64_t* pk_off, const int32_t* pk_len,
+                                   const uint8_t* pk_kind, const uint32_t* pk_crc, uint8_t* dst,
+                                   const uint64_t* dst_off, const int32_t* dst_cap, int32_t* ret,
+                                   uint32_t nblocks, uint32_t max_cap, void* stream) {
+    g_err.clear();
+    if (nblocks == 0) return 0;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    // a stored entry is no longer than the block it decodes to; capacity unknown: a workgroup per entry
+    const uint32_t hint = max_cap ? max_cap : 256 * 64;
+    const uint64_t words = lz4e::crc_partial_words(hint, nblocks);
+    // one allocation: got[n], masked[n], partial[words], shown[n]
+    uint32_t* scratch = nullptr;
+    if (!hip_ok(hipMallocAsync((void**)&scratch, sizeof(uint32_t) * (2 * (size_t)nblocks + (size_t)words) + nblocks, s),
+                "verified unpack scratch"))
+        return -1;
+    uint32_t* got = scratch;
+    int32_t* masked = reinterpret_cast<int32_t*>(scratch + nblocks);
+    uint32_t* partial = scratch + 2 * (size_t)nblocks;
+    uint8_t* shown = reinterpret_cast<uint8_t*>(partial + words);
+    const lz4e::CrcBatch c{packed, pk_off, packed, pk_off, pk_kind, pk_len, got, nblocks, hint};
+    lz4e::DecompressBatch d{packed, pk_off, masked, dst, dst_off, dst_cap, ret, nblocks, max_cap};
+    lz4e::UnpackRawBatch r{packed, pk_off, pk_len, shown, dst, dst_off, dst_cap, ret, nblocks, max_cap};
+    const bool ok =
+        hip_ok(lz4e::launch_crc(c, partial, s), "verified unpack crc launch") &&
+        hip_ok(lz4e::launch_unpack_verify_mask(pk_len, pk_kind, pk_crc, got, nblocks, masked, shown, s),
+               "verified unpack mask launch") &&
+        hip_ok(lz4e::launch_decompress(d, s), "verified unpack decompress launch") &&
+        hip_ok(lz4e::launch_unpack_raw(r, s), "verified unpack raw launch") &&
+        hip_ok(lz4e::launch_unpack_verify_ret(shown, nblocks, ret, s), "verified unpack ret launch");
+    (void)hipFreeAsync(scratch, s);
+    return ok ? 0 : -1;
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------

@@ -33,6 +33,7 @@ __all__ = [
     "GpuUnavailable", "LIB_PATH", "EXPORTED_SYMBOLS", "HostArena", "GuardReport",
     "register_host_memory", "unregister_host_memory", "zero_copy_requests",
     "pack_batch_dev", "unpack_batch_dev", "PACK_FRAME", "PACK_RAW",
+    "crc32c_batch_dev", "pack_crc_batch_dev", "unpack_verified_batch_dev", "UNPACK_BAD_CRC",
 ]
 
 PAGE_SIZE = 4096
@@ -54,6 +55,7 @@ EXPORTED_SYMBOLS = (
     "lz4e_decompress_batch_dict", "lz4e_compress_batch_dev_dict", "lz4e_decompress_batch_dev_dict",
     "lz4e_register_host_memory", "lz4e_unregister_host_memory",
     "lz4e_pack_batch_dev", "lz4e_unpack_batch_dev",
+    "lz4e_crc32c_batch_dev", "lz4e_pack_crc_batch_dev", "lz4e_unpack_verified_batch_dev",
 )
 
 
@@ -176,6 +178,13 @@ def lib() -> ctypes.CDLL:
         L.lz4e_pack_batch_dev.restype = I32
         L.lz4e_unpack_batch_dev.argtypes = [P] * 8 + [U32, U32, P]
         L.lz4e_unpack_batch_dev.restype = I32
+    if hasattr(L, "lz4e_crc32c_batch_dev"):
+        L.lz4e_crc32c_batch_dev.argtypes = [P] * 4 + [U32, U32, P]
+        L.lz4e_crc32c_batch_dev.restype = I32
+        L.lz4e_pack_crc_batch_dev.argtypes = [P] * 7 + [U32, U32, P]
+        L.lz4e_pack_crc_batch_dev.restype = I32
+        L.lz4e_unpack_verified_batch_dev.argtypes = [P] * 9 + [U32, U32, P]
+        L.lz4e_unpack_verified_batch_dev.restype = I32
     _lib = L
     return L
 
@@ -612,9 +621,12 @@ def _check_dev(n: int, **tensors) -> None:
             "src_off": torch.int64, "dst_off": torch.int64, "src_len": torch.int32,
             "dst_cap": torch.int32, "ret": torch.int32, "aux": torch.int32,
             "frames": torch.uint8, "fr_off": torch.int64, "packed": torch.uint8,
-            "pk_off": torch.int64, "pk_len": torch.int32, "pk_kind": torch.uint8}
+            "pk_off": torch.int64, "pk_len": torch.int32, "pk_kind": torch.uint8,
+            "pk_crc": torch.int32, "data": torch.uint8, "off": torch.int64, "len": torch.int32,
+            "crc": torch.int32}
     per_block = {"src_off": 1, "dst_off": 1, "src_len": 1, "dst_cap": 1, "ret": 1,
-                 "table_type": 1, "aux": 2, "fr_off": 1, "pk_len": 1, "pk_kind": 1}
+                 "table_type": 1, "aux": 2, "fr_off": 1, "pk_len": 1, "pk_kind": 1,
+                 "pk_crc": 1, "off": 1, "len": 1, "crc": 1}
     dev = None
     for name, t in tensors.items():
         if t is None:
@@ -732,3 +744,68 @@ def unpack_batch_dev(packed, pk_off, pk_len, pk_kind, dst, dst_off, dst_cap, ret
                                     _ptr(dst_off), _ptr(dst_cap), _ptr(ret), n, max(0, int(max_cap)), stream)
     if r != 0:
         raise RuntimeError("lz4e_unpack_batch_dev: " + last_error())
+
+
+UNPACK_BAD_CRC = -2147483647  # LZ4E_UNPACK_BAD_CRC (INT32_MIN + 1)
+
+
+def crc32c_batch_dev(data, off, len_, crc, max_len: Optional[int] = None, stream=None) -> None:
+    """lz4e_crc32c_batch_dev on torch tensors (launch only): crc[i] = CRC-32C
+    of the len_[i] bytes at data + off[i].
+
+    data: uint8; off: int64; len_: int32; crc: int32 (torch has no unsigned
+    32-bit arithmetic: the column's bit patterns; ``crc.cpu().numpy().view
+    ("uint32")`` gives the values).  ``max_len`` is a sizing hint (default:
+    read from len_, which synchronises); no result depends on it."""
+    import torch
+    n = int(len_.numel())
+    _check_dev(n, data=data, off=off, len=len_, crc=crc)
+    if max_len is None:
+        max_len = max(0, int(len_.max().item())) if n else 0
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    r = lib().lz4e_crc32c_batch_dev(_ptr(data), _ptr(off), _ptr(len_), _ptr(crc), n, int(max_len), stream)
+    if r != 0:
+        raise RuntimeError("lz4e_crc32c_batch_dev: " + last_error())
+
+
+def pack_crc_batch_dev(frames, fr_off, src, src_off, pk_len, pk_kind, pk_crc, max_len: Optional[int] = None,
+                       stream=None) -> None:
+    """lz4e_pack_crc_batch_dev on torch tensors (launch only): the index's
+    checksum column, after pack_batch_dev on the same stream with the same
+    frames / fr_off / src / src_off.  pk_crc: int32 (bit patterns, as
+    crc32c_batch_dev's).  ``max_len`` as for pack_batch_dev (default: read
+    from pk_len, which synchronises)."""
+    import torch
+    n = int(pk_len.numel())
+    _check_dev(n, frames=frames, fr_off=fr_off, src=src, src_off=src_off, pk_len=pk_len, pk_kind=pk_kind,
+               pk_crc=pk_crc)
+    if max_len is None:
+        max_len = max(0, int(pk_len.max().item())) if n else 0
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    r = lib().lz4e_pack_crc_batch_dev(_ptr(frames), _ptr(fr_off), _ptr(src), _ptr(src_off), _ptr(pk_len),
+                                      _ptr(pk_kind), _ptr(pk_crc), n, int(max_len), stream)
+    if r != 0:
+        raise RuntimeError("lz4e_pack_crc_batch_dev: " + last_error())
+
+
+def unpack_verified_batch_dev(packed, pk_off, pk_len, pk_kind, pk_crc, dst, dst_off, dst_cap, ret, stream=None,
+                              max_cap: Optional[int] = None) -> None:
+    """lz4e_unpack_verified_batch_dev on torch tensors (launch only):
+    unpack_batch_dev that checks each entry against pk_crc first; an entry
+    whose stored bytes do not match gets ret UNPACK_BAD_CRC and nothing is
+    written for it.  ``max_cap`` as for unpack_batch_dev."""
+    import torch
+    n = int(pk_len.numel())
+    _check_dev(n, packed=packed, pk_off=pk_off, pk_len=pk_len, pk_kind=pk_kind, pk_crc=pk_crc, dst=dst,
+               dst_off=dst_off, dst_cap=dst_cap, ret=ret)
+    if max_cap is None:
+        max_cap = int(dst_cap.max().item()) if n else 0
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    r = lib().lz4e_unpack_verified_batch_dev(_ptr(packed), _ptr(pk_off), _ptr(pk_len), _ptr(pk_kind), _ptr(pk_crc),
+                                             _ptr(dst), _ptr(dst_off), _ptr(dst_cap), _ptr(ret), n,
+                                             max(0, int(max_cap)), stream)
+    if r != 0:
+        raise RuntimeError("lz4e_unpack_verified_batch_dev: " + last_error())

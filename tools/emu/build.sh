@@ -10,6 +10,9 @@
 #   EMU_PACK=1 tools/emu/build.sh [flags] -> $EMU_BUILD/emu_pack (standalone: the
 #                                           packed frame store's kernels,
 #                                           csrc/lz4e_pack.hip)
+#   EMU_CRC=1 tools/emu/build.sh [flags]  -> $EMU_BUILD/emu_crc (standalone: the
+#                                           store's checksum kernels,
+#                                           csrc/lz4e_crc.hip)
 # Pass extra flags, e.g. -fsanitize=address,undefined or -DLZ4E_SPIN_MAX=1.
 set -e
 here=$(cd "$(dirname "$0")" && pwd)
@@ -18,7 +21,10 @@ b="${EMU_BUILD:-$here/build}"
 mkdir -p "$b"
 CXX=${CXX:-/opt/rocm/llvm/bin/clang++}
 FLAGS=(-std=c++20 -O1 -g -pthread -x c++ -DLZ4E_EMU -I "$here/include" -I "$csrc")
-if [ -n "$EMU_PACK" ]; then
+if [ -n "$EMU_CRC" ]; then
+    $CXX "${FLAGS[@]}" -I "$here/../../include" "$@" "$here/emu_crc.cpp" -o "$b/emu_crc"
+    echo "built $b/emu_crc"
+elif [ -n "$EMU_PACK" ]; then
     $CXX "${FLAGS[@]}" -I "$here/../../include" "$@" "$here/emu_pack.cpp" -o "$b/emu_pack"
     echo "built $b/emu_pack"
 elif [ -n "$EMU_SG" ]; then

@@ -1,0 +1,482 @@
+// Lane emulator of the packed frame store's checksum kernels (debug/test
+// tooling, tools/emu): compiles the unmodified csrc/lz4e_crc.hip as host C++
+// and runs crc_team_kernel, crc_combine_kernel, unpack_verify_mask_kernel and
+// unpack_verify_ret_kernel under the same emulated <hip/hip_runtime.h> as the
+// other kernel files; csrc/lz4e_pack.hip is compiled in for the raw copy that
+// runs between the two verify kernels (the decoders that run there too are
+// emu_main's business: here their part is played by a stand-in that returns
+// -1 for a masked length of 0 and a marker otherwise).  Stand-alone (its own
+// main): built by EMU_CRC=1 build.sh, run by tests/test_emulator_crc.py under
+// ASan + UBSan.
+//
+// The kernels read the CALLER's memory at byte granularity.  So every entry
+// here is its own heap allocation that ends exactly at its last byte (ASan's
+// redzone follows it), placed at a chosen alignment mod 16 as in emu_pack.cpp.
+// An entry that must not be read is an allocation of 0 bytes or an offset
+// outside every allocation.  Expected values come from ref_crc below, a
+// bitwise restatement of CRC-32C that shares nothing with the kernel's tables.
+//
+// crc_team_kernel fills a table in LDS behind a barrier and XORs across
+// lanes, so a workgroup of it is 256 host threads (4 emulated waves) that
+// live as long as the program; workgroups run one after the other.  The
+// other kernels have neither, so their lanes run one after the other on the
+// calling thread.
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <memory>
+#include <thread>
+#include <vector>
+
+#include <hip/hip_runtime.h>
+#undef __shared__
+#define __shared__ static
+void emu_launch_named(const char* kernel, uint32_t nblocks, uint32_t threads, std::function<void()> body);
+#undef hipLaunchKernelGGL
+#define hipLaunchKernelGGL(k, grid, block, lds, stream, ...) \
+    emu_launch_named(#k, (grid).x, (block).x, [&]() { k(__VA_ARGS__); })
+
+#include "lz4e_crc.hip"
+#include "lz4e_pack.hip"
+
+#include "lz4e.h"
+
+#if defined(__has_feature)
+#if __has_feature(address_sanitizer)
+#include <sanitizer/asan_interface.h>
+#define EMU_POISON(p, n) __asan_poison_memory_region((p), (n))
+#define EMU_UNPOISON(p, n) __asan_unpoison_memory_region((p), (n))
+#endif
+#endif
+#ifndef EMU_POISON
+#define EMU_POISON(p, n) ((void)0)
+#define EMU_UNPOISON(p, n) ((void)0)
+#endif
+
+thread_local EmuWave* g_emu_wave;
+thread_local uint32_t g_emu_lane;
+thread_local EmuBarrier* g_emu_group;
+dim3 blockIdx, gridDim;
+thread_local dim3 threadIdx;
+
+namespace {
+constexpr uint32_t kLanes = 256;
+struct LanePool {
+    EmuBarrier start{kLanes + 1}, end{kLanes + 1}, group{kLanes};
+    EmuWave waves[kLanes / 64];
+    std::function<void()>* body = nullptr;
+    bool quit = false;
+    std::vector<std::thread> th;
+    LanePool() {
+        for (uint32_t t = 0; t < kLanes; ++t)
+            th.emplace_back([this, t]() {
+                g_emu_wave = &waves[t / 64];
+                g_emu_lane = t % 64;
+                g_emu_group = &group;
+                threadIdx = dim3(t);
+                for (;;) {
+                    start.arrive_and_wait();
+                    if (quit) return;
+                    (*body)();
+                    end.arrive_and_wait();
+                }
+            });
+    }
+    ~LanePool() {
+        quit = true;
+        start.arrive_and_wait();
+        for (auto& x : th) x.join();
+    }
+};
+uint64_t g_groups_run = 0;
+}  // namespace
+
+void emu_launch(uint32_t nblocks, uint32_t threads, std::function<void()> body) {
+    static LanePool pool;
+    if (threads != kLanes) abort();
+    gridDim = dim3(nblocks);
+    pool.body = &body;
+    for (uint32_t b = 0; b < nblocks; ++b) {
+        blockIdx = dim3(b);
+        pool.start.arrive_and_wait();
+        pool.end.arrive_and_wait();
+    }
+    g_groups_run += nblocks;
+}
+
+void emu_launch_named(const char* kernel, uint32_t nblocks, uint32_t threads, std::function<void()> body) {
+    if (strstr(kernel, "crc_team")) return emu_launch(nblocks, threads, body);
+    if (strstr(kernel, "pack_tile") || strstr(kernel, "pack_index")) abort();  // not run here
+    gridDim = dim3(nblocks);
+    for (uint32_t b = 0; b < nblocks; ++b) {
+        blockIdx = dim3(b);
+        for (uint32_t t = 0; t < threads; ++t) {
+            threadIdx = dim3(t);
+            g_emu_lane = t % 64;
+            body();
+        }
+    }
+}
+
+namespace {
+
+int g_failures = 0;
+#define CHECK(c, ...)                        \
+    do {                                     \
+        if (!(c)) {                          \
+            fprintf(stderr, "FAIL: " __VA_ARGS__); \
+            fprintf(stderr, "\n");           \
+            g_failures++;                    \
+        }                                    \
+    } while (0)
+
+uint32_t g_rng = 2463534242u;
+uint32_t rnd32() {
+    g_rng = g_rng * 1664525u + 1013904223u;
+    return g_rng >> 8;
+}
+uint8_t rnd() { return (uint8_t)rnd32(); }
+
+// CRC-32C bit by bit.
+uint32_t ref_crc(const uint8_t* p, size_t n) {
+    uint32_t c = 0xFFFFFFFFu;
+    for (size_t i = 0; i < n; ++i) {
+        c ^= p[i];
+        for (int k = 0; k < 8; ++k) c = (c >> 1) ^ ((c & 1u) ? 0x82F63B78u : 0u);
+    }
+    return c ^ 0xFFFFFFFFu;
+}
+
+constexpr uint8_t kCanary = 0xC3, kFill = 0x5A;
+constexpr uint32_t kHugeHint = 0x7E000000u;
+
+// n bytes at alignment `align` (mod 16), ending where their heap block ends.
+struct Buf {
+    uint8_t* base;
+    uint8_t* p;
+    size_t align, n;
+    Buf(size_t align_, size_t n_) : align(align_ & 15), n(n_) {
+        base = static_cast<uint8_t*>(malloc(align + n));
+        if (!base) abort();
+        p = base + align;
+        memset(base, kCanary, align);
+        EMU_POISON(base, align & ~size_t(7));
+    }
+    Buf(const Buf&) = delete;
+    Buf& operator=(const Buf&) = delete;
+    ~Buf() {
+        EMU_UNPOISON(base, align & ~size_t(7));
+        free(base);
+    }
+    void fill_random() {
+        for (size_t i = 0; i < n; ++i) p[i] = rnd();
+    }
+    void fill(uint8_t v) { memset(p, v, n); }
+    bool all(uint8_t v) const {
+        for (size_t i = 0; i < n; ++i)
+            if (p[i] != v) return false;
+        return true;
+    }
+    bool canary_ok() const {
+        for (size_t i = align & ~size_t(7); i < align; ++i)
+            if (base[i] != kCanary) return false;
+        return true;
+    }
+    template <class T>
+    T* as() {
+        return reinterpret_cast<T*>(p);
+    }
+};
+typedef std::unique_ptr<Buf> BufP;
+
+const uint8_t* lowest(const std::vector<BufP>& v) {
+    const uint8_t* lo = nullptr;
+    for (const BufP& b : v)
+        if (!lo || b->p < lo) lo = b->p;
+    return lo;
+}
+
+// launch_crc with the scratch lz4e_host.hip would take from the pool: an
+// exact-size allocation, so a partial written outside it is a report.
+void run_crc(const lz4e::CrcBatch& a, const char* what) {
+    const uint64_t words = lz4e::crc_partial_words(a.max_len, a.nblocks);
+    Buf partial(0, 4 * (size_t)words);
+    partial.fill(kFill);
+    CHECK(lz4e::launch_crc(a, words ? partial.as<uint32_t>() : nullptr, nullptr) == hipSuccess, "%s: launch", what);
+}
+
+struct CEntry {
+    int32_t len;  // <= 0: an allocation of 0 bytes
+    uint32_t align;
+};
+
+// lz4e_crc32c_batch_dev's kernels on entries that are allocations of their
+// own, once per hint; every column must equal the bitwise restatement.
+void crc_case(const char* what, const std::vector<CEntry>& es, const std::vector<uint32_t>& hints) {
+    const uint32_t n = (uint32_t)es.size();
+    std::vector<BufP> bufs;
+    std::vector<uint32_t> want(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        bufs.emplace_back(new Buf(es[i].align, es[i].len > 0 ? (size_t)es[i].len : 0));
+        bufs[i]->fill_random();
+        want[i] = ref_crc(bufs[i]->p, bufs[i]->n);
+    }
+    const uint8_t* data = lowest(bufs);
+    Buf off(0, 8 * (size_t)n), len(0, 4 * (size_t)n);
+    for (uint32_t i = 0; i < n; ++i) {
+        off.as<uint64_t>()[i] = (uint64_t)(bufs[i]->p - data);
+        len.as<int32_t>()[i] = es[i].len;
+    }
+    for (uint32_t hint : hints) {
+        Buf crc(0, 4 * (size_t)n);
+        crc.fill(kFill);
+        const lz4e::CrcBatch a{data, off.as<uint64_t>(), nullptr, nullptr, nullptr, len.as<int32_t>(),
+                               crc.as<uint32_t>(), n, hint};
+        run_crc(a, what);
+        for (uint32_t i = 0; i < n; ++i)
+            CHECK(crc.as<uint32_t>()[i] == want[i], "%s: hint %u (team shift %u), entry %u of %u (len %d at %u mod 16): %08x, expected %08x",
+                  what, hint, lz4e::crc_team_shift(hint, n), i, n, es[i].len, es[i].align, crc.as<uint32_t>()[i], want[i]);
+    }
+    for (uint32_t i = 0; i < n; ++i) CHECK(bufs[i]->canary_ok(), "%s: canary of entry %u", what, i);
+}
+
+// The same bytes between different neighbours, inside one allocation each.
+void context_case(uint32_t body_len, uint32_t hint) {
+    std::vector<uint8_t> body(body_len);
+    for (auto& b : body) b = rnd();
+    const uint32_t want = ref_crc(body.data(), body_len);
+    const uint32_t before[4] = {0, 1, 37, 4096}, after[4] = {0, 64, 5, 1};
+    std::vector<BufP> bufs;
+    Buf off(0, 8 * 4), len(0, 4 * 4), crc(0, 4 * 4);
+    for (uint32_t k = 0; k < 4; ++k) {
+        bufs.emplace_back(new Buf(k * 5, before[k] + body_len + after[k]));
+        bufs[k]->fill_random();
+        memcpy(bufs[k]->p + before[k], body.data(), body_len);
+    }
+    const uint8_t* data = lowest(bufs);
+    for (uint32_t k = 0; k < 4; ++k) {
+        off.as<uint64_t>()[k] = (uint64_t)(bufs[k]->p + before[k] - data);
+        len.as<int32_t>()[k] = (int32_t)body_len;
+    }
+    crc.fill(kFill);
+    const lz4e::CrcBatch a{data, off.as<uint64_t>(), nullptr, nullptr, nullptr, len.as<int32_t>(), crc.as<uint32_t>(), 4, hint};
+    run_crc(a, "context");
+    for (uint32_t k = 0; k < 4; ++k)
+        CHECK(crc.as<uint32_t>()[k] == want, "context: %u bytes after %u and before %u others: %08x, expected %08x", body_len,
+              before[k], after[k], crc.as<uint32_t>()[k], want);
+}
+
+struct PEntry {
+    uint8_t kind;
+    uint32_t len, frame_align, src_align;
+};
+
+// lz4e_pack_crc_batch_dev's launch: what an entry's kind does not read is 0 bytes long.
+void pack_crc_case(const char* what, const std::vector<PEntry>& es, const std::vector<uint32_t>& hints) {
+    const uint32_t n = (uint32_t)es.size();
+    std::vector<BufP> slots, srcs;
+    std::vector<uint32_t> want(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const bool frame = es[i].kind == LZ4E_PACK_FRAME;
+        slots.emplace_back(new Buf(es[i].frame_align, frame ? es[i].len : 0));
+        srcs.emplace_back(new Buf(es[i].src_align, frame ? 0 : es[i].len));
+        slots[i]->fill_random();
+        srcs[i]->fill_random();
+        want[i] = frame ? ref_crc(slots[i]->p, es[i].len) : ref_crc(srcs[i]->p, es[i].len);
+    }
+    const uint8_t* frames = lowest(slots);
+    const uint8_t* src = lowest(srcs);
+    Buf fr_off(0, 8 * (size_t)n), src_off(0, 8 * (size_t)n), pk_len(0, 4 * (size_t)n), pk_kind(0, n);
+    for (uint32_t i = 0; i < n; ++i) {
+        fr_off.as<uint64_t>()[i] = (uint64_t)(slots[i]->p - frames);
+        src_off.as<uint64_t>()[i] = (uint64_t)(srcs[i]->p - src);
+        pk_len.as<int32_t>()[i] = (int32_t)es[i].len;
+        pk_kind.as<uint8_t>()[i] = es[i].kind;
+    }
+    for (uint32_t hint : hints) {
+        Buf crc(0, 4 * (size_t)n);
+        crc.fill(kFill);
+        const lz4e::CrcBatch a{frames, fr_off.as<uint64_t>(), src, src_off.as<uint64_t>(), pk_kind.as<uint8_t>(),
+                               pk_len.as<int32_t>(), crc.as<uint32_t>(), n, hint};
+        run_crc(a, what);
+        for (uint32_t i = 0; i < n; ++i)
+            CHECK(crc.as<uint32_t>()[i] == want[i], "%s: hint %u, entry %u (kind %u, len %u): %08x, expected %08x", what, hint, i,
+                  es[i].kind, es[i].len, crc.as<uint32_t>()[i], want[i]);
+    }
+    bool canaries = true;
+    for (uint32_t i = 0; i < n; ++i) canaries &= slots[i]->canary_ok() && srcs[i]->canary_ok();
+    CHECK(canaries, "%s: canary", what);
+}
+
+struct VEntry {
+    uint8_t kind;
+    int32_t len, cap;
+    bool good_crc;
+    bool outside;  // pk_off points outside every allocation
+};
+constexpr int32_t kDecoded = 424242;  // the stand-in decoder's ret for an entry it was shown
+
+// lz4e_unpack_verified_batch_dev's composition on an image of the given
+// entries (align 1): checksum, mask, stand-in decoders, raw copy, ret.
+void verify_case(const char* what, const std::vector<VEntry>& es, uint32_t packed_align, uint32_t hint) {
+    const uint32_t n = (uint32_t)es.size();
+    Buf pk_off(0, 8 * ((size_t)n + 1)), pk_len(0, 4 * (size_t)n), pk_kind(0, n), pk_crc(0, 4 * (size_t)n),
+        dst_off(0, 8 * (size_t)n), dst_cap(0, 4 * (size_t)n), ret(0, 4 * (size_t)n), masked(0, 4 * (size_t)n),
+        got(0, 4 * (size_t)n), shown(0, n);
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        pk_off.as<uint64_t>()[i] = es[i].outside ? ((uint64_t)1 << 46) + i : at;
+        if (!es[i].outside) at += (uint64_t)(es[i].len > 0 ? es[i].len : 0);
+        pk_len.as<int32_t>()[i] = es[i].len;
+        pk_kind.as<uint8_t>()[i] = es[i].kind;
+        dst_cap.as<int32_t>()[i] = es[i].cap;
+    }
+    pk_off.as<uint64_t>()[n] = at;
+    Buf packed(packed_align, at);
+    packed.fill_random();
+    for (uint32_t i = 0; i < n; ++i) {
+        const bool readable = !es[i].outside && es[i].len >= 0;
+        const uint32_t c = readable ? ref_crc(packed.p + pk_off.as<uint64_t>()[i], (size_t)es[i].len) : 0x1234567u;
+        pk_crc.as<uint32_t>()[i] = es[i].good_crc ? c : c ^ (1u << (i % 32));
+    }
+    std::vector<BufP> dsts;
+    for (uint32_t i = 0; i < n; ++i) {
+        dsts.emplace_back(new Buf(i * 3, es[i].cap > 0 ? (size_t)es[i].cap : 0));
+        dsts[i]->fill(kFill);
+    }
+    uint8_t* dst = const_cast<uint8_t*>(lowest(dsts));
+    for (uint32_t i = 0; i < n; ++i) dst_off.as<uint64_t>()[i] = (uint64_t)(dsts[i]->p - dst);
+    got.fill(kFill);
+    masked.fill(kFill);
+    shown.fill(kFill);
+    const lz4e::CrcBatch c{packed.p, pk_off.as<uint64_t>(), packed.p, pk_off.as<uint64_t>(), pk_kind.as<uint8_t>(),
+                           pk_len.as<int32_t>(), got.as<uint32_t>(), n, hint};
+    run_crc(c, what);
+    CHECK(lz4e::launch_unpack_verify_mask(pk_len.as<int32_t>(), pk_kind.as<uint8_t>(), pk_crc.as<uint32_t>(),
+                                          got.as<uint32_t>(), n, masked.as<int32_t>(), shown.as<uint8_t>(),
+                                          nullptr) == hipSuccess,
+          "%s: mask launch", what);
+    for (uint32_t i = 0; i < n; ++i)  // the decoders: -1 for srcSize 0 before they read or write anything
+        ret.as<int32_t>()[i] = masked.as<int32_t>()[i] == 0 ? -1 : kDecoded;
+    const lz4e::UnpackRawBatch r{packed.p, pk_off.as<uint64_t>(), pk_len.as<int32_t>(), shown.as<uint8_t>(), dst,
+                                 dst_off.as<uint64_t>(), dst_cap.as<int32_t>(), ret.as<int32_t>(), n, hint};
+    CHECK(lz4e::launch_unpack_raw(r, nullptr) == hipSuccess, "%s: raw launch", what);
+    CHECK(lz4e::launch_unpack_verify_ret(shown.as<uint8_t>(), n, ret.as<int32_t>(), nullptr) == hipSuccess, "%s: ret launch",
+          what);
+    for (uint32_t i = 0; i < n; ++i) {
+        const VEntry& e = es[i];
+        const int32_t m = masked.as<int32_t>()[i], rr = ret.as<int32_t>()[i];
+        const bool valid = (e.kind == LZ4E_PACK_FRAME || e.kind == LZ4E_PACK_RAW) && e.len >= 0;
+        if (!valid) {
+            CHECK(rr == -1 && m == 0 && dsts[i]->all(kFill), "%s: invalid entry %u (kind %u, len %d): ret %d, masked %d", what, i,
+                  e.kind, e.len, rr, m);
+        } else if (!e.good_crc) {
+            CHECK(rr == LZ4E_UNPACK_BAD_CRC && m == 0 && dsts[i]->all(kFill), "%s: entry %u with a wrong checksum (kind %u, len %d, cap %d): ret %d, masked %d",
+                  what, i, e.kind, e.len, e.cap, rr, m);
+        } else if (e.kind == LZ4E_PACK_FRAME) {
+            CHECK(m == e.len && rr == (e.len ? kDecoded : -1) && dsts[i]->all(kFill), "%s: clean frame entry %u (len %d): ret %d, masked %d",
+                  what, i, e.len, rr, m);
+        } else if (e.len <= e.cap) {
+            bool good = rr == e.len && m == 0 && (e.len == 0 || memcmp(dsts[i]->p, packed.p + pk_off.as<uint64_t>()[i], (size_t)e.len) == 0);
+            for (size_t k = (size_t)e.len; k < dsts[i]->n; ++k) good &= dsts[i]->p[k] == kFill;
+            CHECK(good, "%s: clean raw entry %u (len %d, cap %d): ret %d", what, i, e.len, e.cap, rr);
+        } else {
+            CHECK(rr == -1 && m == 0 && dsts[i]->all(kFill), "%s: raw entry %u over capacity (len %d, cap %d): ret %d", what, i, e.len,
+                  e.cap, rr);
+        }
+        CHECK(dsts[i]->canary_ok(), "%s: bytes before destination %u written", what, i);
+    }
+    CHECK(packed.canary_ok(), "%s: packed canary", what);
+}
+
+const int32_t kLens[] = {0, 1, 3, 4, 5, 15, 16, 17, 31, 33, 63, 64, 65, 511, 512, 4096, 4097, 70000};
+constexpr uint32_t kSmallLens = 13;  // 0 ... 65
+
+}  // namespace
+
+int main() {
+    {  // the restatement itself
+        const uint8_t nine[] = {'1', '2', '3', '4', '5', '6', '7', '8', '9'};
+        uint8_t z[32] = {0};
+        CHECK(ref_crc(nine, 9) == 0xE3069283u && ref_crc(z, 32) == 0x8A9136AAu && ref_crc(z, 0) == 0, "ref_crc");
+    }
+    // ---- every length, three hints on the same batch ----
+    {
+        std::vector<CEntry> es;
+        uint32_t k = 0;
+        for (int32_t len : kLens) es.push_back({len, (5 * k++ + 3) & 15});
+        es.push_back({-7, 0});  // a negative length reads nothing
+        crc_case("lengths", es, {1u, 70000u, kHugeHint});
+    }
+    // ---- every start residue for the lengths up to 65; the last hint splits them over workgroups ----
+    {
+        std::vector<CEntry> es;
+        for (uint32_t li = 0; li < kSmallLens; ++li)
+            for (uint32_t a = 0; a < 16; ++a) es.push_back({kLens[li], a});
+        crc_case("residues", es, {1u, 65u, 4096u, 64u << 9});
+    }
+    // ---- every team size: one byte under, at and over one vector per thread, the hint's 64 bytes per
+    //      thread, a wave's 64 threads busy and a workgroup's 256 ----
+    for (uint32_t shift = 4; shift <= 14; ++shift) {
+        const uint32_t nt = 1u << shift, hint = 64u << shift;
+        if (lz4e::crc_team_shift(hint, 1) != shift) {
+            CHECK(false, "team shift %u is not what hint %u picks", shift, hint);
+            continue;
+        }
+        std::vector<CEntry> es;
+        uint32_t k = shift;
+        for (uint32_t at : {16 * nt, 64 * nt, 16u * 64, 64u * 64, 16u * 256, 64u * 256, 80u * 256})
+            for (int32_t d = -1; d <= 1; ++d)
+                if (at <= 64 * nt) es.push_back({(int32_t)at + d, (7 * k++) & 15});
+        crc_case("team sizes", es, {hint});
+    }
+    // ---- the same bytes with different neighbours ----
+    context_case(1000, 1000);
+    context_case(33, 1);
+    context_case(5000, 64u << 10);
+    // ---- entry counts: none, one, around a workgroup's 16, 4, 2 and 1 entries ----
+    for (uint32_t hint : {1u, 64u << 6, 64u << 7, 64u << 8, 64u << 9})
+        for (uint32_t n : {0u, 1u, 2u, 3u, 4u, 5u, 15u, 16u, 17u, 33u}) {
+            std::vector<CEntry> es;
+            for (uint32_t i = 0; i < n; ++i) es.push_back({(int32_t)(rnd32() % 41), rnd32() & 15});
+            crc_case("counts", es, {hint});
+        }
+    // ---- pack_crc: frame and raw entries; the other side of each is 0 bytes long ----
+    {
+        std::vector<PEntry> es;
+        uint32_t k = 0;
+        for (int32_t len : kLens) {
+            if (len) es.push_back({LZ4E_PACK_FRAME, (uint32_t)len, (k * 3 + 1) & 15, (k * 7) & 15});
+            es.push_back({LZ4E_PACK_RAW, (uint32_t)len, (k * 5) & 15, (k * 11 + 5) & 15});
+            ++k;
+        }
+        pack_crc_case("pack_crc", es, {1u, 70000u, 64u << 9});
+    }
+    // ---- verified unpack: mask, raw copy and ret ----
+    for (uint32_t hint : {4096u, 64u << 9}) {
+        std::vector<VEntry> es;
+        for (int32_t len : {0, 1, 17, 512, 4097}) {
+            es.push_back({LZ4E_PACK_FRAME, len, len + 40, true, false});   // clean
+            es.push_back({LZ4E_PACK_RAW, len, len, true, false});
+            es.push_back({LZ4E_PACK_FRAME, len, len + 40, false, false});  // a wrong pk_crc
+            es.push_back({LZ4E_PACK_RAW, len, len + 9, false, false});
+            es.push_back({LZ4E_PACK_RAW, len + 1, len, true, false});      // over capacity, good and bad checksum
+            es.push_back({LZ4E_PACK_RAW, len + 1, len, false, false});
+            es.push_back({2, len, len + 40, true, true});                  // unknown kinds and a negative length:
+            es.push_back({255, len, len, false, true});                    // the offset points nowhere
+            es.push_back({LZ4E_PACK_RAW, -5 - len, 64, true, true});
+            es.push_back({LZ4E_PACK_FRAME, -1 - len, 64, false, true});
+        }
+        verify_case("verify", es, hint == 4096u ? 0 : 11, hint);
+    }
+    verify_case("verify, no entry", {}, 0, 4096);
+    if (g_failures) {
+        fprintf(stderr, "emu_crc: %d failures\n", g_failures);
+        return 1;
+    }
+    fprintf(stderr, "emu_crc: %llu workgroups of crc_team_kernel\n", (unsigned long long)g_groups_run);
+    printf("emu_crc ok\n");
+    return 0;
+}
