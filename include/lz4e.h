@@ -271,6 +271,73 @@ int lz4e_decompress_batch_dev(const uint8_t *src, const uint64_t *src_off,
 			      int32_t *ret, uint32_t nblocks, void *stream);
 
 /*
+ * Partial decoding: stop as soon as `target` bytes exist (a READ of a few
+ * KiB at the front of a 64 KiB chunk does not pay for the chunk).  The
+ * reference decoder carries it -- LZ4E_decompress_generic's earlyEnd_directive
+ * partialDecoding, lz4e/lz4e_decompress.c:229-246, 276-282, 306-314, 384-405
+ * -- but its one exported entry (:462-469) never instantiates it.  These
+ * entry points are that function with endOnInputSize, partial_decode, noDict
+ * and outputSize = target, line for line, return codes included (bytes
+ * written, at most target, or -(ip - src) - 1).  Against the full decode:
+ *
+ *  - a literal run that would end past the target is cut there; the (cut)
+ *    run must still lie inside the input (:230-246); after it the decode ends
+ *    when the target is reached or fewer than 3 input bytes remain (:281),
+ *    and goes on to the offset otherwise, so a frame that breaks the
+ *    end-of-block rules can be accepted;
+ *  - after the unchanged offset and length checks, a match that would end
+ *    past target - 12 is cut to min(length, target - op) bytes, and the decode
+ *    ends when the target is reached (:388-405); the full decoder's "last 5
+ *    bytes are literals" error (:425-431) cannot occur;
+ *  - the special cases (:113-120) are unchanged: target 0 gives -1 unless the
+ *    frame is the single byte 00 (the reference's behaviour, which upstream
+ *    LZ4 does not share).
+ *
+ * For a frame the full decoder accepts with n bytes of output, target k >= 1
+ * gives min(k, n) and the first min(k, n) bytes of that output.  Nothing is
+ * written outside [dest, dest + target).
+ *
+ * One deviation: the reference skips its LZ4_write32(op, offset) in partial
+ * mode (:309-314), so a match with offset 0 would repeat whatever the
+ * destination held before.  Here it yields zeros, as in the full decoders.
+ *
+ * No partial entry point takes a dictionary (in the reference's extDict
+ * branch a cut match does not end the decode, :339-378, and the next token
+ * may lie past the frame).
+ *
+ * LZ4E_decompress_safe_partial decodes to min(targetOutputSize, dstCapacity)
+ * bytes, as LZ4_decompress_safe_partial does (a negative value of either:
+ * -1).  Concurrent calls are coalesced like LZ4E_decompress_safe's, in
+ * launches of their own.
+ */
+int LZ4E_decompress_safe_partial(const char *source, char *dest,
+				 int compressedSize, int targetOutputSize,
+				 int dstCapacity);
+
+/* Host batch: lz4e_decompress_batch with target[i] in place of cap[i];
+ * ret[i] receives the partial decode's value. */
+int lz4e_decompress_partial_batch(const char *const *src, const int *csize,
+				  char *const *dst, const int *target,
+				  int *ret, int n);
+
+/*
+ * Device-resident partial batch: lz4e_decompress_batch_dev2's arguments,
+ * placement contract (any byte alignment of inputs and outputs, nothing
+ * written outside [dst + dst_off[i], + dst_cap[i])) and stream-capture
+ * legality (launches and stream-ordered pool scratch only); dst_cap[i] is
+ * block i's target and capacity at once.  The decoder is chosen as there,
+ * except that the group decoder has no partial form: the one-wave decoder
+ * takes its place, and LZ4E_DECOMPRESS_MODE=g is read as auto.
+ */
+int lz4e_decompress_partial_batch_dev(const uint8_t *src,
+				      const uint64_t *src_off,
+				      const int32_t *src_len, uint8_t *dst,
+				      const uint64_t *dst_off,
+				      const int32_t *dst_cap, int32_t *ret,
+				      uint32_t nblocks, uint32_t max_cap,
+				      void *stream);
+
+/*
  * Dictionary mode.  The reference stubs its dictionary
  * path out (lz4e/lz4e_compress.c:250-266, 315-324, 393-419, 472-482; the
  * dictionary fields of LZ4E_stream_t, lz4e/include/lz4e.h:36-40) and its
@@ -513,6 +580,48 @@ int lz4e_unpack_batch_dev(const uint8_t *packed, const uint64_t *pk_off,
 			  uint8_t *dst, const uint64_t *dst_off,
 			  const int32_t *dst_cap, int32_t *ret, uint32_t nblocks,
 			  uint32_t max_cap, void *stream);
+
+/*
+ * Packed frame store: range reads.  A READ asks for a few KiB at some offset
+ * inside a chunk; request j reads bytes [lo[j], lo[j] + len[j]) of entry
+ * sel[j] (sel == NULL: entry j; an entry may be named by many requests) into
+ * dst + dst_off[j], without decoding the entry past lo[j] + len[j]:
+ *
+ *   invalid  sel[j] >= nentries, an unknown pk_kind, a negative pk_len, a
+ *            negative lo[j] or len[j]: ret[j] = -1, nothing is read or
+ *            written (checked first).
+ *   len[j] == 0   ret[j] = 0, nothing is read or written.
+ *   LZ4E_PACK_FRAME  d = the partial decode of the frame with target
+ *            lo[j] + len[j] (lz4e_decompress_partial_batch_dev: values, error
+ *            codes and decoder choice, from max_end and nreq).  d < 0:
+ *            ret[j] = d and nothing is written.  Otherwise ret[j] =
+ *            max(0, d - lo[j]) and those bytes, [lo[j], d) of the entry's
+ *            data, are written.
+ *   LZ4E_PACK_RAW    d = min(pk_len, lo[j] + len[j]), copied straight from
+ *            the image; ret[j] and the bytes as above.
+ *   writes   stay inside [dst_off[j], dst_off[j] + ret[j]), exactly.
+ *
+ * max_end bounds lo[] + len[] (a request past it is read as if it ended at
+ * max_end; at most 0x7FFFFFF0).  Composition, as for unpack: a small kernel
+ * gathers (offset, length, target) per request, the partial launch decodes
+ * into scratch, a team copy (exact at both ends) delivers the ranges and the
+ * raw entries and sets ret; no kernel waits on another workgroup.  Launches
+ * only, legal under stream capture.  Footprint: one allocation from the
+ * stream-ordered pool (hipMallocAsync on `stream`, freed behind the last
+ * launch) of nreq x (roundup(max_end, 16) + 28) + 16 bytes -- a request costs
+ * scratch for its whole prefix, so for reads far into large entries
+ * lz4e_unpack_batch_dev may be the better call.  If the pool refuses it the
+ * call returns -1 with lz4e_last_error() set and nothing is launched.
+ * The checksum column is not consulted (no verified range read).
+ * Returns 0 on successful launches, -22 for max_end above the limit.
+ */
+int lz4e_unpack_range_batch_dev(const uint8_t *packed, const uint64_t *pk_off,
+				const int32_t *pk_len, const uint8_t *pk_kind,
+				uint32_t nentries, const uint32_t *sel,
+				const int32_t *lo, const int32_t *len,
+				uint8_t *dst, const uint64_t *dst_off,
+				int32_t *ret, uint32_t nreq, uint32_t max_end,
+				void *stream);
 
 /*
  * Packed frame store: integrity.

@@ -293,7 +293,11 @@ LZ4E_DEV uint32_t fast_next(uint32_t t, uint32_t p) {
 // bytes.
 // kVecExt: length-extension runs by 256-byte vector scans (the pipelined
 // decoder; the one-wave decoder keeps the byte loop, see kOneWaveVecExt).
-template <bool kVecExt = false, class Lap = NoLap>
+// kPartial: the reference's partial_decode instance (oend = the target size;
+// include/lz4e.h, LZ4E_decompress_safe_partial).  Its branches (:229-246,
+// 281, 388-405) all lie on the scalar path -- the shortcut needs
+// op <= oend - 32 -- and each of its exits sets P.done; the value is P.op.
+template <bool kVecExt = false, bool kPartial = false, class Lap = NoLap>
 LZ4E_DEV ParseResult parse_batch(Parse& P, Batch& b, uint32_t lane,
                                  int32_t cap_out = (int32_t)kWave * kFastSeqMax, Lap lap = Lap()) {
     const int32_t iend = P.iend, oend = P.oend;
@@ -361,9 +365,12 @@ LZ4E_DEV ParseResult parse_batch(Parse& P, Batch& b, uint32_t lane,
         // and for offsets < 8 the _copy_match end check (:422-431); a source
         // in the dictionary takes _copy_match: offset inside dictionary +
         // block (:299-302), then the extDict end check (:341-346).
+        // Partial: _copy_match has no end check (:388-405), but a match of
+        // an offset < 8 that ends at oend ends the decode there (:402-403):
+        // that sequence is the scalar path's.
+        const bool end_ok = kPartial ? m_k + M < oend : m_k + M <= oend - 5;
         const bool ok = cand && o_k <= oend - kFastSeqMax && incl <= cap_out &&
-                        (m_k >= off ? (off >= 8 || m_k + M <= oend - 5)
-                                    : (m_k - off + P.D >= 0 && m_k + M <= oend - 5));
+                        (m_k >= off ? (off >= 8 || end_ok) : (m_k - off + P.D >= 0 && end_ok));
         const uint64_t okm = ballot(ok);
         const uint32_t nf = (~okm) ? ctz64(~okm) : kWave;  // first failing lane
         if (nf > 0) {
@@ -431,15 +438,30 @@ LZ4E_DEV ParseResult parse_batch(Parse& P, Batch& b, uint32_t lane,
         lit_op = op;
         L = length;
         if (ugt(cpy, oend - 12) || ugt(iln, iend - 8)) {
-            if (iln != (uint32_t)iend || ugt(cpy, oend)) goto fail;
+            if constexpr (kPartial) {
+                // :229-246: the run is cut at oend, and must lie in the input
+                if (ugt(cpy, oend)) L = length = (uint32_t)(oend - op);
+                if (ugt((uint32_t)ip + length, iend)) goto fail;
+                ip += (int32_t)length;
+                op += (int32_t)length;
+                // :281: the end, unless output and an offset's input remain
+                if (op == oend || ip >= iend - 2) {
+                    length = 0;
+                    P.done = true;
+                    goto record;
+                }
+            } else {
+                if (iln != (uint32_t)iend || ugt(cpy, oend)) goto fail;
+                ip += (int32_t)length;
+                op += (int32_t)length;
+                length = 0;
+                P.done = true;  // final literal run: no match
+                goto record;
+            }
+        } else {
             ip += (int32_t)length;
-            op += (int32_t)length;
-            length = 0;
-            P.done = true;  // final literal run: no match
-            goto record;
+            op = (int32_t)cpy;
         }
-        ip += (int32_t)length;
-        op = (int32_t)cpy;
     }
     offset = (int32_t)(win.byte(ip) | (win.byte(ip + 1) << 8));  // :291-296
     ip += 2;
@@ -471,8 +493,21 @@ copy_match_checks:
             } while (s == 255);
         }
     }
-    if (ugt((uint32_t)op + length + 4, oend - 5)) goto fail;
-    length += 4;
+    if constexpr (kPartial) {
+        // :388-405: a match that ends past oend - 12 is cut at oend (to 1
+        // byte or more: a match is only reached with op < oend) and ends the
+        // decode when it reaches oend; the last-literals rule (:425-431) is
+        // not checked
+        length += 4;
+        if (ugt((uint32_t)op + length, oend - 12)) {
+            const uint32_t room = (uint32_t)(oend - op);
+            length = length < room ? length : room;
+            P.done = length == room;
+        }
+    } else {
+        if (ugt((uint32_t)op + length + 4, oend - 5)) goto fail;
+        length += 4;
+    }
 
 record:
     {

@@ -177,8 +177,9 @@ struct WaveStamps {
 // sink, the span buffer of the fast batches and its jump table.  kLdsOut:
 // the whole output is assembled in obuf (kSmallBuf bytes; outSize <=
 // kSmallOut, no dictionary) and stored at the end; a fast batch's span is
-// then obuf itself.
-template <bool kStamps, bool kLdsOut = false>
+// then obuf itself.  kPartial: outSize is the target of a partial decode
+// (parse_batch); the copies are the same, a cut match may be 1..3 bytes.
+template <bool kStamps, bool kLdsOut = false, bool kPartial = false>
 LZ4E_DEV void decode_block(const uint8_t* in, int32_t srcSize, uint8_t* gout, int32_t outSize,
                            int32_t* ret_slot, uint64_t* dbg, uint32_t lane, lu8* span_buf,
                            lu32* ring, lu16* jump, int32_t dict, lu8* sinkb, lu8* obuf = nullptr,
@@ -203,7 +204,7 @@ LZ4E_DEV void decode_block(const uint8_t* in, int32_t srcSize, uint8_t* gout, in
 
     for (;;) {
         Batch b;
-        const ParseResult pr = parse_batch<kOneWaveVecExt>(
+        const ParseResult pr = parse_batch<kOneWaveVecExt, kPartial>(
             P, b, lane, kLdsOut ? kSmallBatchOut : (int32_t)kWave * kFastSeqMax);
         if (pr == kParseFail) {
             if (lane == 0) *ret_slot = -P.ip - 1;
@@ -357,8 +358,9 @@ LZ4E_DEV bool special_case(const uint8_t* in, int32_t srcSize, int32_t outSize, 
 }
 
 // kSmall: the LDS-output form for blocks of at most kSmallOut bytes without
-// a dictionary (other blocks of the launch take the HBM form).
-template <bool kStamps, bool kSmall = false>
+// a dictionary (other blocks of the launch take the HBM form).  kPartial:
+// dst_cap[b] is block b's target size.
+template <bool kStamps, bool kSmall = false, bool kPartial = false>
 __global__ __launch_bounds__(64) void decompress_kernel(const uint8_t* __restrict__ src,
                                                         const uint64_t* __restrict__ src_off,
                                                         const int32_t* __restrict__ src_len,
@@ -387,13 +389,13 @@ __global__ __launch_bounds__(64) void decompress_kernel(const uint8_t* __restric
     const int32_t dict = dict_of(dict_len, b);
     if (kSmall && dict == 0 && outSize <= kSmallOut && srcSize <= kSmallOut) {
         lu8* obuf = (lu8*)(smem + kSink);
-        decode_block<kStamps, true>(in, srcSize, out, outSize, ret + b, d, lane, obuf, nullptr,
+        decode_block<kStamps, true, kPartial>(in, srcSize, out, outSize, ret + b, d, lane, obuf, nullptr,
                                     (lu16*)(obuf + kSmallBuf), 0, (lu8*)smem, obuf,
                                     obuf + kSmallBuf + kSmallJump);
     } else {
         lu8* sinkb = (lu8*)(smem + kRing + kRingPad);
-        decode_block<kStamps>(in, srcSize, out, outSize, ret + b, d, lane, sinkb + kSink, (lu32*)smem,
-                              (lu16*)(sinkb + kSink + kSpan), dict, sinkb);
+        decode_block<kStamps, false, kPartial>(in, srcSize, out, outSize, ret + b, d, lane, sinkb + kSink,
+                                               (lu32*)smem, (lu16*)(sinkb + kSink + kSpan), dict, sinkb);
     }
 }
 
@@ -463,7 +465,9 @@ __global__ __launch_bounds__(64) void decompress_resume_kernel(
 }
 
 // The pipelined decoder (lz4e_dec_pipe.h): wave 0 parses, waves 1..3 copy.
-template <bool kStamps>
+// kPartial (compile time: the kernel sits at its register cap): dst_cap[b]
+// is block b's target size; only the parser differs.
+template <bool kStamps, bool kPartial = false>
 __global__ __launch_bounds__(kPipeWaves * kWave, kPipeMinWg) void decompress_pipe_kernel(
     const uint8_t* __restrict__ src, const uint64_t* __restrict__ src_off,
     const int32_t* __restrict__ src_len, uint8_t* dst, const uint64_t* __restrict__ dst_off,
@@ -515,7 +519,7 @@ __global__ __launch_bounds__(kPipeWaves * kWave, kPipeMinWg) void decompress_pip
         for (;;) {
             Batch bt;
             const int32_t lo = P.op;
-            const ParseResult pr = parse_batch<true>(P, bt, lane, kPipeOut, [&](int k) {
+            const ParseResult pr = parse_batch<true, kPartial>(P, bt, lane, kPipeOut, [&](int k) {
                 if (kStamps) st.lap(true, kStPWin + k);
             });
             st.lap(kStamps, kStParse);
@@ -706,9 +710,15 @@ struct DecodeWeight {
     }
 };
 
-template <bool kStamps>
+// kPartial: a partial launch (DecompressBatch::partial, no dictionary):
+// the same choice with the group decoder, which has no partial form,
+// replaced by the one-wave decoder (LZ4E_DECOMPRESS_MODE=g: auto).
+template <bool kStamps, bool kPartial = false>
 hipError_t launch_impl(const DecompressBatch& a, hipStream_t stream, uint64_t* dbg) {
     if (a.nblocks == 0) return hipSuccess;
+    if constexpr (kPartial) {
+        if (a.dict_len || a.mode == kDecGroupNoBail) return hipErrorInvalidValue;
+    }
     // LZ4E_DECOMPRESS_MODE=w|p|s|g (one-wave, pipelined, LDS form, group)
     // overrides auto mode for A/B experiments; any other value is auto.
     static const char* env = getenv("LZ4E_DECOMPRESS_MODE");
@@ -717,9 +727,10 @@ hipError_t launch_impl(const DecompressBatch& a, hipStream_t stream, uint64_t* d
         mode = env[0] == 'w'   ? kDecWave
                : env[0] == 'p' ? kDecPipe
                : env[0] == 's' ? kDecSmall
-               : env[0] == 'g' ? kDecGroup
+               : env[0] == 'g' ? (kPartial ? kDecAuto : kDecGroup)
                                : kDecAuto;
     if (mode == kDecAuto) mode = pick_decoder(a.max_cap, a.nblocks);
+    if (kPartial && mode == kDecGroup) mode = kDecWave;
     if (mode == kDecPipe) {
         const int om = launch_order_mode(false);
         uint32_t* order = nullptr;
@@ -731,14 +742,14 @@ hipError_t launch_impl(const DecompressBatch& a, hipStream_t stream, uint64_t* d
             (void)hipGetLastError();  // a failed pool allocation only costs the ordering
             order = nullptr;
         }
-        hipLaunchKernelGGL((decompress_pipe_kernel<kStamps>), dim3(a.nblocks), dim3(kPipeWaves * kWave),
+        hipLaunchKernelGGL((decompress_pipe_kernel<kStamps, kPartial>), dim3(a.nblocks), dim3(kPipeWaves * kWave),
                            0, stream, a.src, a.src_off, a.src_len, a.dst, a.dst_off, a.dst_cap, a.ret,
                            a.nblocks, dbg, a.dict_len, (const uint32_t*)order);
         const hipError_t err = hipGetLastError();
         if (order) (void)hipFreeAsync(order, stream);
         return err;
     }
-    if (mode == kDecGroup || mode == kDecGroupNoBail) {
+    if (!kPartial && (mode == kDecGroup || mode == kDecGroupNoBail)) {
         // hand-over list (count + 3 words per block); without it (or in the
         // no-hand-over test mode) every group decodes its block to the end
         uint32_t* ho = nullptr;
@@ -764,11 +775,11 @@ hipError_t launch_impl(const DecompressBatch& a, hipStream_t stream, uint64_t* d
         return err;
     }
     if (mode == kDecSmall)
-        hipLaunchKernelGGL((decompress_kernel<kStamps, true>), dim3(a.nblocks), dim3(kWave), 0, stream,
+        hipLaunchKernelGGL((decompress_kernel<kStamps, true, kPartial>), dim3(a.nblocks), dim3(kWave), 0, stream,
                            a.src, a.src_off, a.src_len, a.dst, a.dst_off, a.dst_cap, a.ret, a.nblocks,
                            dbg, a.dict_len);
     else
-        hipLaunchKernelGGL((decompress_kernel<kStamps>), dim3(a.nblocks), dim3(kWave), 0, stream,
+        hipLaunchKernelGGL((decompress_kernel<kStamps, false, kPartial>), dim3(a.nblocks), dim3(kWave), 0, stream,
                            a.src, a.src_off, a.src_len, a.dst, a.dst_off, a.dst_cap, a.ret, a.nblocks,
                            dbg, a.dict_len);
     return hipGetLastError();
@@ -777,11 +788,12 @@ hipError_t launch_impl(const DecompressBatch& a, hipStream_t stream, uint64_t* d
 }  // namespace
 
 hipError_t launch_decompress(const DecompressBatch& a, hipStream_t stream) {
-    return launch_impl<false>(a, stream, nullptr);
+    return a.partial ? launch_impl<false, true>(a, stream, nullptr) : launch_impl<false>(a, stream, nullptr);
 }
 
+// (the stamped build has no partial form)
 hipError_t launch_decompress_stamped(const DecompressBatch& a, hipStream_t stream, uint64_t* dbg) {
-    return launch_impl<true>(a, stream, dbg);
+    return a.partial ? hipErrorInvalidValue : launch_impl<true>(a, stream, dbg);
 }
 
 }  // namespace lz4e

@@ -46,6 +46,11 @@ struct DecompressBatch {
     // right before dst + dst_off[i] as its dictionary (extDict semantics of
     // lz4e_decompress.c:299-302, 339-378; <= 64 KiB of it is ever read).
     const int32_t* dict_len = nullptr;
+    // Partial decode (include/lz4e.h, LZ4E_decompress_safe_partial):
+    // dst_cap[i] is block i's target size.  No dictionary, and never the
+    // group decoder, which has no partial form: auto mode and
+    // LZ4E_DECOMPRESS_MODE=g take the one-wave decoder in its place.
+    bool partial = false;
 };
 
 // (3 was the streaming decoder, removed in round 4; 4 and 5 the chunked and
@@ -156,6 +161,40 @@ struct UnpackRawBatch {
     uint32_t max_cap;  // upper bound of dst_cap[] (0: unknown)
 };
 hipError_t launch_unpack_raw(const UnpackRawBatch& a, hipStream_t stream);
+
+// Range read of the packed store (include/lz4e.h,
+// lz4e_unpack_range_batch_dev): request j wants bytes [lo[j], lo[j] + len[j])
+// of entry sel[j] (sel null: entry j).  launch_range_gather writes the
+// partial launch's descriptors -- g_off / g_len / g_tgt: the frame and the
+// target min(lo + len, max_end), or 0 / 0 / 0 for a request no decoder may
+// touch; s_off[j] = j * slot, its scratch slot (slot >= max_end) -- and
+// launch_range_deliver, behind that launch (whose values are g_ret), copies
+// the wanted bytes out of the slots, or out of the image for raw entries,
+// and sets ret.
+struct RangeBatch {
+    const uint8_t* packed;
+    const uint64_t* pk_off;
+    const int32_t* pk_len;
+    const uint8_t* pk_kind;
+    uint32_t nentries;
+    const uint32_t* sel;  // nullable
+    const int32_t* lo;
+    const int32_t* len;
+    uint8_t* dst;
+    const uint64_t* dst_off;
+    int32_t* ret;
+    uint32_t nreq;
+    uint32_t max_end;  // upper bound of lo[] + len[]
+    uint64_t slot;     // bytes of scratch per request
+    uint8_t* scratch;
+    uint64_t* g_off;
+    int32_t* g_len;
+    int32_t* g_tgt;
+    uint64_t* s_off;
+    int32_t* g_ret;
+};
+hipError_t launch_range_gather(const RangeBatch& a, hipStream_t stream);
+hipError_t launch_range_deliver(const RangeBatch& a, hipStream_t stream);
 
 // CRC-32C of every entry of a batch (lz4e_crc.hip; include/lz4e.h
 // lz4e_crc32c_batch_dev, lz4e_pack_crc_batch_dev,

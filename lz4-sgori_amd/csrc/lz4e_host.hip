@@ -580,6 +580,12 @@ Coalescer<DecompressCall>& decompress_calls() {
     static Coalescer<DecompressCall> c[kMaxDevices];
     return c[current_device()];
 }
+// Partial single calls queue apart from the full ones: a coalesced batch is
+// one launch, and a launch is either partial or full.
+Coalescer<DecompressCall>& partial_calls() {
+    static Coalescer<DecompressCall> c[kMaxDevices];
+    return c[current_device()];
+}
 
 }  // namespace
 
@@ -673,8 +679,10 @@ uint64_t decode_staging_bytes(int csize, int cap) { return decode_staging(csize,
 // staged right after the last <= 64 KiB of its dictionary (the decoders read
 // sources before the output from there), and the whole staging image goes
 // H2D.
+// partial: cap[i] is block i's target size (a partial launch; no dictionaries).
 int decompress_batch_impl(const char* const* src, const int* csize, char* const* dst, const int* cap,
-                          int* ret, int n, const char* const* dicts, const int* dict_sizes) {
+                          int* ret, int n, const char* const* dicts, const int* dict_sizes,
+                          bool partial = false) {
     if (n <= 0) return 0;
     g_err.clear();
     for (int i = 0; i < n; ++i) ret[i] = -1;
@@ -721,6 +729,7 @@ int decompress_batch_impl(const char* const* src, const int* csize, char* const*
                             R,
                             (uint32_t)std::max(0, *std::max_element(cap, cap + n))};
     if (dicts) a.dict_len = reinterpret_cast<const int32_t*>(dd + m_dl);
+    a.partial = partial;
     const uint64_t h2d = dicts ? obase + d : m_rt;  // the dictionaries live among the outputs
     bool ok = hip_ok(hipMemcpyAsync(dd, hd, h2d, hipMemcpyHostToDevice, c.stream), "H2D") &&
               hip_ok(lz4e::launch_decompress(a, c.stream), "decompress launch") &&
@@ -758,7 +767,7 @@ int lz4e_decompress_batch(const char* const* src, const int* csize, char* const*
 // One coalesced batch of single decompress calls; a batch that fails as a
 // whole (staging, launch, a watchdog on some block) is bisected, so that
 // only the caller whose block failed sees the failure.
-static void run_decompress_calls(DecompressCall** batch, size_t n) {
+static void run_decompress_calls(DecompressCall** batch, size_t n, bool partial = false) {
     std::vector<const char*> src(n);
     std::vector<char*> dst(n);
     std::vector<int> cs(n), cap(n), ret(n, -1);
@@ -769,10 +778,10 @@ static void run_decompress_calls(DecompressCall** batch, size_t n) {
         cap[i] = batch[i]->cap;
     }
     const int r = decompress_batch_impl(src.data(), cs.data(), dst.data(), cap.data(), ret.data(), (int)n,
-                                        nullptr, nullptr);
+                                        nullptr, nullptr, partial);
     if (r < 0 && n > 1) {
-        run_decompress_calls(batch, n / 2);
-        run_decompress_calls(batch + n / 2, n - n / 2);
+        run_decompress_calls(batch, n / 2, partial);
+        run_decompress_calls(batch + n / 2, n - n / 2, partial);
         return;
     }
     for (size_t i = 0; i < n; ++i) {
@@ -790,6 +799,33 @@ int LZ4E_decompress_safe(const char* source, char* dest, int compressedSize, int
         [](DecompressCall** batch, size_t n) {
             maybe_inject_fault();
             run_decompress_calls(batch, n);
+        },
+        [](DecompressCall* c, const std::string& why) {
+            c->ret = -1;
+            c->err = why;
+        });
+    g_err = call.err;
+    return call.ret;
+}
+
+int lz4e_decompress_partial_batch(const char* const* src, const int* csize, char* const* dst,
+                                  const int* target, int* ret, int n) {
+    return decompress_batch_impl(src, csize, dst, target, ret, n, nullptr, nullptr, true);
+}
+
+int LZ4E_decompress_safe_partial(const char* source, char* dest, int compressedSize, int targetOutputSize,
+                                 int dstCapacity) {
+    const int target = std::min(targetOutputSize, dstCapacity);
+    if (target < 0) {
+        set_err("LZ4E_decompress_safe_partial: negative target or capacity");
+        return -1;
+    }
+    DecompressCall call{source, dest, compressedSize, target};
+    partial_calls().submit(
+        &call,
+        [](DecompressCall** batch, size_t n) {
+            maybe_inject_fault();
+            run_decompress_calls(batch, n, true);
         },
         [](DecompressCall* c, const std::string& why) {
             c->ret = -1;
@@ -913,6 +949,34 @@ int lz4e_decompress_batch_dev2(const uint8_t* src, const uint64_t* src_off, cons
                : -1;
 }
 
+int lz4e_decompress_partial_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                      uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
+                                      int32_t* ret, uint32_t nblocks, uint32_t max_cap, void* stream) {
+    g_err.clear();
+    lz4e::DecompressBatch a{src, src_off, src_len, dst, dst_off, dst_cap, ret, nblocks, max_cap};
+    a.partial = true;
+    return hip_ok(lz4e::launch_decompress(a, static_cast<hipStream_t>(stream)), "partial decompress launch")
+               ? 0
+               : -1;
+}
+
+// Diagnostic (not part of include/lz4e.h): lz4e_decompress_partial_batch_dev
+// with a forced decoder (0 auto, 1 one wave per block, 2 pipelined, 6 LDS
+// form; 7, the group decoder, has no partial form and runs as 1).
+int lz4e_debug_decompress_partial(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                  uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap, int32_t* ret,
+                                  uint32_t nblocks, uint32_t max_cap, void* stream, uint32_t mode) {
+    if (mode != lz4e::kDecAuto && mode != lz4e::kDecWave && mode != lz4e::kDecPipe && mode != lz4e::kDecSmall &&
+        mode != lz4e::kDecGroup)
+        return -1;
+    g_err.clear();
+    lz4e::DecompressBatch a{src, src_off, src_len, dst, dst_off, dst_cap, ret, nblocks, max_cap, mode};
+    a.partial = true;
+    return hip_ok(lz4e::launch_decompress(a, static_cast<hipStream_t>(stream)), "partial decompress launch")
+               ? 0
+               : -1;
+}
+
 // The round-1 signature (no max_cap: the pipelined decoder for every block).
 int lz4e_decompress_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                               uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
@@ -996,6 +1060,40 @@ int lz4e_unpack_batch_dev(const uint8_t* packed, const uint64_t* pk_off, const i
                     hip_ok(lz4e::launch_decompress(d, s), "unpack decompress launch") &&
                     hip_ok(lz4e::launch_unpack_raw(r, s), "unpack raw launch");
     (void)hipFreeAsync(masked, s);
+    return ok ? 0 : -1;
+}
+
+// Range read: gather, one partial launch into stream-ordered scratch, team
+// copy.  One allocation: nreq slots of roundup(max_end, 16) bytes, then the
+// partial launch's descriptors (28 bytes per request).
+int lz4e_unpack_range_batch_dev(const uint8_t* packed, const uint64_t* pk_off, const int32_t* pk_len,
+                                const uint8_t* pk_kind, uint32_t nentries, const uint32_t* sel,
+                                const int32_t* lo, const int32_t* len, uint8_t* dst, const uint64_t* dst_off,
+                                int32_t* ret, uint32_t nreq, uint32_t max_end, void* stream) {
+    g_err.clear();
+    if (nreq == 0) return 0;
+    if (max_end > 0x7FFFFFF0u) {
+        set_err("lz4e_unpack_range_batch_dev: max_end above 0x7FFFFFF0");
+        return -22;
+    }
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint64_t slot = align16((uint64_t)max_end);
+    const uint64_t data = slot * nreq;  // a multiple of 16: the descriptors behind it are aligned
+    uint8_t* scratch = nullptr;
+    if (!hip_ok(hipMallocAsync((void**)&scratch, data + 28ull * nreq + 16, s), "range read scratch")) return -1;
+    uint64_t* g_off = reinterpret_cast<uint64_t*>(scratch + data);
+    uint64_t* s_off = g_off + nreq;
+    int32_t* g_len = reinterpret_cast<int32_t*>(s_off + nreq);
+    int32_t* g_tgt = g_len + nreq;
+    int32_t* g_ret = g_tgt + nreq;
+    const lz4e::RangeBatch r{packed, pk_off, pk_len, pk_kind, nentries, sel,   lo,    len,   dst,   dst_off,
+                             ret,    nreq,   max_end, slot,   scratch,  g_off, g_len, g_tgt, s_off, g_ret};
+    lz4e::DecompressBatch d{packed, g_off, g_len, scratch, s_off, g_tgt, g_ret, nreq, max_end};
+    d.partial = true;
+    const bool ok = hip_ok(lz4e::launch_range_gather(r, s), "range gather launch") &&
+                    hip_ok(lz4e::launch_decompress(d, s), "range decompress launch") &&
+                    hip_ok(lz4e::launch_range_deliver(r, s), "range deliver launch");
+    (void)hipFreeAsync(scratch, s);
     return ok ? 0 : -1;
 }
 

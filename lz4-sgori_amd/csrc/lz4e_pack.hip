@@ -196,6 +196,79 @@ __global__ __launch_bounds__(256) void unpack_raw_kernel(
     if (ok) sg_copy(dst + dst_off[i], packed + pk_off[i], (uint32_t)len, t, nt);
 }
 
+// Range read (lz4e_unpack_range_batch_dev), in front of the partial launch:
+// request j's frame as the decoders see it.  A request the decoders must not
+// touch -- not a frame entry, invalid, or empty -- gets length 0 and target 0:
+// each decoder returns for it before it reads or writes anything.  The
+// target is clamped to max_end, the size of a request's scratch slot.
+struct RangeReq {
+    uint32_t entry;
+    bool valid;  // the entry exists, its kind is known, its length and the range are not negative
+};
+LZ4E_DEV RangeReq range_req(const uint32_t* sel, const int32_t* lo, const int32_t* len, const int32_t* pk_len,
+                            const uint8_t* pk_kind, uint32_t nentries, uint64_t j) {
+    const uint32_t e = sel ? sel[j] : (uint32_t)j;
+    bool ok = e < nentries && lo[j] >= 0 && len[j] >= 0;
+    if (ok) ok = (pk_kind[e] == kPackFrame || pk_kind[e] == kPackRaw) && pk_len[e] >= 0;
+    return RangeReq{e, ok};
+}
+LZ4E_DEV int32_t range_end(const int32_t* lo, const int32_t* len, uint32_t max_end, uint64_t j) {
+    const uint64_t end = (uint64_t)(uint32_t)lo[j] + (uint32_t)len[j];
+    return (int32_t)(end < max_end ? end : max_end);
+}
+
+__global__ __launch_bounds__(256) void range_gather_kernel(
+    const uint64_t* __restrict__ pk_off, const int32_t* __restrict__ pk_len, const uint8_t* __restrict__ pk_kind,
+    uint32_t nentries, const uint32_t* __restrict__ sel, const int32_t* __restrict__ lo,
+    const int32_t* __restrict__ len, uint32_t nreq, uint32_t max_end, uint64_t slot, uint64_t* __restrict__ g_off,
+    int32_t* __restrict__ g_len, int32_t* __restrict__ g_tgt, uint64_t* __restrict__ s_off) {
+    const uint64_t j = (uint64_t)blockIdx.x * kPackThreads + threadIdx.x;
+    if (j >= nreq) return;
+    const RangeReq q = range_req(sel, lo, len, pk_len, pk_kind, nentries, j);
+    const bool dec = q.valid && pk_kind[q.entry] == kPackFrame && len[j] > 0;
+    g_off[j] = dec ? pk_off[q.entry] : 0;
+    g_len[j] = dec ? pk_len[q.entry] : 0;
+    g_tgt[j] = dec ? range_end(lo, len, max_end, j) : 0;
+    s_off[j] = j * slot;
+}
+
+// Behind the partial launch, teams as in pack_copy_kernel: the wanted bytes
+// of each request from its scratch slot (frame entries) or straight from the
+// image (raw entries), and ret.
+__global__ __launch_bounds__(256) void range_deliver_kernel(
+    const uint8_t* __restrict__ packed, const uint64_t* __restrict__ pk_off, const int32_t* __restrict__ pk_len,
+    const uint8_t* __restrict__ pk_kind, uint32_t nentries, const uint32_t* __restrict__ sel,
+    const int32_t* __restrict__ lo, const int32_t* __restrict__ len, uint8_t* __restrict__ dst,
+    const uint64_t* __restrict__ dst_off, int32_t* __restrict__ ret, uint32_t nreq, uint32_t max_end,
+    const uint8_t* __restrict__ scratch, uint64_t slot, const int32_t* __restrict__ g_ret, uint32_t team_shift) {
+    const uint64_t g = (uint64_t)blockIdx.x * kPackThreads + threadIdx.x;
+    const uint64_t j = g >> team_shift;
+    if (j >= nreq) return;
+    const uint32_t nt = 1u << team_shift, t = (uint32_t)g & (nt - 1);
+    const RangeReq q = range_req(sel, lo, len, pk_len, pk_kind, nentries, j);
+    if (!q.valid || len[j] == 0) {
+        if (t == 0) ret[j] = q.valid ? 0 : -1;
+        return;
+    }
+    const int32_t end = range_end(lo, len, max_end, j);
+    const uint8_t* from;
+    int32_t d;
+    if (pk_kind[q.entry] == kPackFrame) {
+        d = g_ret[j];  // the partial decode with target `end`
+        from = scratch + j * slot;
+    } else {
+        d = pk_len[q.entry] < end ? pk_len[q.entry] : end;
+        from = packed + pk_off[q.entry];
+    }
+    if (d < 0) {
+        if (t == 0) ret[j] = d;
+        return;
+    }
+    const int32_t cnt = d > lo[j] ? d - lo[j] : 0;
+    if (t == 0) ret[j] = cnt;
+    sg_copy(dst + dst_off[j], from + lo[j], (uint64_t)cnt, t, nt);
+}
+
 // Threads per entry: about 64 bytes for each of the largest entry, a power
 // of two from 16 (a quarter wave: tiny entries, many to a workgroup) to 16384
 // (64 workgroups on one entry); fewer where the grid would pass 2^31 - 1.
@@ -243,6 +316,23 @@ hipError_t launch_unpack_raw(const UnpackRawBatch& a, hipStream_t stream) {
     const uint32_t shift = a.max_cap ? team_shift_for(a.max_cap, a.nblocks) : team_shift_for(256 * 64, a.nblocks);
     hipLaunchKernelGGL(unpack_raw_kernel, team_grid(a.nblocks, shift), dim3(kPackThreads), 0, stream, a.packed,
                        a.pk_off, a.pk_len, a.pk_kind, a.dst, a.dst_off, a.dst_cap, a.ret, a.nblocks, shift);
+    return hipGetLastError();
+}
+
+hipError_t launch_range_gather(const RangeBatch& a, hipStream_t stream) {
+    if (a.nreq == 0) return hipSuccess;
+    hipLaunchKernelGGL(range_gather_kernel, team_grid(a.nreq, 0), dim3(kPackThreads), 0, stream, a.pk_off, a.pk_len,
+                       a.pk_kind, a.nentries, a.sel, a.lo, a.len, a.nreq, a.max_end, a.slot, a.g_off, a.g_len,
+                       a.g_tgt, a.s_off);
+    return hipGetLastError();
+}
+
+hipError_t launch_range_deliver(const RangeBatch& a, hipStream_t stream) {
+    if (a.nreq == 0) return hipSuccess;
+    const uint32_t shift = team_shift_for(a.max_end, a.nreq);
+    hipLaunchKernelGGL(range_deliver_kernel, team_grid(a.nreq, shift), dim3(kPackThreads), 0, stream, a.packed,
+                       a.pk_off, a.pk_len, a.pk_kind, a.nentries, a.sel, a.lo, a.len, a.dst, a.dst_off, a.ret,
+                       a.nreq, a.max_end, (const uint8_t*)a.scratch, a.slot, (const int32_t*)a.g_ret, shift);
     return hipGetLastError();
 }
 

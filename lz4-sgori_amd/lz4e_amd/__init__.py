@@ -34,6 +34,8 @@ __all__ = [
     "register_host_memory", "unregister_host_memory", "zero_copy_requests",
     "pack_batch_dev", "unpack_batch_dev", "PACK_FRAME", "PACK_RAW",
     "crc32c_batch_dev", "pack_crc_batch_dev", "unpack_verified_batch_dev", "UNPACK_BAD_CRC",
+    "decompress_safe_partial", "decompress_partial_batch", "decompress_partial_batch_dev",
+    "unpack_range_batch_dev",
 ]
 
 PAGE_SIZE = 4096
@@ -56,6 +58,8 @@ EXPORTED_SYMBOLS = (
     "lz4e_register_host_memory", "lz4e_unregister_host_memory",
     "lz4e_pack_batch_dev", "lz4e_unpack_batch_dev",
     "lz4e_crc32c_batch_dev", "lz4e_pack_crc_batch_dev", "lz4e_unpack_verified_batch_dev",
+    "LZ4E_decompress_safe_partial", "lz4e_decompress_partial_batch", "lz4e_decompress_partial_batch_dev",
+    "lz4e_unpack_range_batch_dev",
 )
 
 
@@ -185,6 +189,17 @@ def lib() -> ctypes.CDLL:
         L.lz4e_pack_crc_batch_dev.restype = I32
         L.lz4e_unpack_verified_batch_dev.argtypes = [P] * 9 + [U32, U32, P]
         L.lz4e_unpack_verified_batch_dev.restype = I32
+    if hasattr(L, "lz4e_decompress_partial_batch_dev"):
+        L.LZ4E_decompress_safe_partial.argtypes = [P, P, I32, I32, I32]
+        L.LZ4E_decompress_safe_partial.restype = I32
+        L.lz4e_decompress_partial_batch.argtypes = [P, P, P, P, P, I32]
+        L.lz4e_decompress_partial_batch.restype = I32
+        L.lz4e_decompress_partial_batch_dev.argtypes = [P, P, P, P, P, P, P, U32, U32, P]
+        L.lz4e_decompress_partial_batch_dev.restype = I32
+        L.lz4e_debug_decompress_partial.argtypes = [P, P, P, P, P, P, P, U32, U32, P, U32]
+        L.lz4e_debug_decompress_partial.restype = I32
+        L.lz4e_unpack_range_batch_dev.argtypes = [P] * 4 + [U32] + [P] * 6 + [U32, U32, P]
+        L.lz4e_unpack_range_batch_dev.restype = I32
     _lib = L
     return L
 
@@ -386,6 +401,19 @@ def decompress_safe(source: bytes, max_decompressed_size: int,
     return r, dst.raw[:max(r, 0)]
 
 
+def decompress_safe_partial(source: bytes, target_output_size: int, dst_capacity: Optional[int] = None,
+                            compressed_size: Optional[int] = None) -> Tuple[int, bytes]:
+    """LZ4E_decompress_safe_partial into a buffer of dst_capacity bytes
+    (default: the target); returns (ret, dest[:max(ret, 0)])."""
+    _require_gpu()
+    cap = target_output_size if dst_capacity is None else dst_capacity
+    csize = len(source) if compressed_size is None else compressed_size
+    dst = ctypes.create_string_buffer(max(cap, 0) + 1)
+    src = ctypes.create_string_buffer(bytes(source), max(len(source), 1))
+    r = lib().LZ4E_decompress_safe_partial(src, dst, csize, target_output_size, cap)
+    return r, dst.raw[:max(r, 0)]
+
+
 def compress_using_dict(src: SgList, dst: SgList, dictionary: bytes,
                         wrkmem: Optional[ctypes.Array] = None) -> int:
     """LZ4E_compress_usingDict (dictionary mode, include/lz4e.h)."""
@@ -477,6 +505,22 @@ def decompress_batch(frames: Sequence[bytes], caps: Sequence[int]) -> List[Tuple
     cp = (ctypes.c_int * n)(*caps)
     rt = (ctypes.c_int * n)()
     if lib().lz4e_decompress_batch(sp, cs, dp, cp, rt, n) < 0:
+        raise GpuUnavailable(last_error())
+    return [(rt[i], dsts[i].raw[:max(rt[i], 0)]) for i in range(n)]
+
+
+def decompress_partial_batch(frames: Sequence[bytes], targets: Sequence[int]) -> List[Tuple[int, bytes]]:
+    """lz4e_decompress_partial_batch over host frames; returns (ret, bytes) per frame."""
+    _require_gpu()
+    n = len(frames)
+    srcs = [ctypes.create_string_buffer(bytes(f), max(len(f), 1)) for f in frames]
+    dsts = [ctypes.create_string_buffer(max(c, 0) + 1) for c in targets]
+    sp = (ctypes.c_void_p * n)(*[ctypes.addressof(s) for s in srcs])
+    dp = (ctypes.c_void_p * n)(*[ctypes.addressof(d) for d in dsts])
+    cs = (ctypes.c_int * n)(*[len(f) for f in frames])
+    cp = (ctypes.c_int * n)(*targets)
+    rt = (ctypes.c_int * n)()
+    if lib().lz4e_decompress_partial_batch(sp, cs, dp, cp, rt, n) < 0:
         raise GpuUnavailable(last_error())
     return [(rt[i], dsts[i].raw[:max(rt[i], 0)]) for i in range(n)]
 
@@ -623,7 +667,7 @@ def _check_dev(n: int, **tensors) -> None:
             "frames": torch.uint8, "fr_off": torch.int64, "packed": torch.uint8,
             "pk_off": torch.int64, "pk_len": torch.int32, "pk_kind": torch.uint8,
             "pk_crc": torch.int32, "data": torch.uint8, "off": torch.int64, "len": torch.int32,
-            "crc": torch.int32}
+            "crc": torch.int32, "sel": torch.int32, "lo": torch.int32}
     per_block = {"src_off": 1, "dst_off": 1, "src_len": 1, "dst_cap": 1, "ret": 1,
                  "table_type": 1, "aux": 2, "fr_off": 1, "pk_len": 1, "pk_kind": 1,
                  "pk_crc": 1, "off": 1, "len": 1, "crc": 1}
@@ -693,6 +737,30 @@ def decompress_batch_dev(src, src_off, src_len, dst, dst_off, dst_cap, ret, stre
         raise RuntimeError("lz4e_decompress_batch_dev2: " + last_error())
 
 
+def decompress_partial_batch_dev(src, src_off, src_len, dst, dst_off, dst_cap, ret, stream=None,
+                                 max_cap: Optional[int] = None, mode: Optional[int] = None) -> None:
+    """lz4e_decompress_partial_batch_dev on torch tensors (launch only):
+    dst_cap[i] is block i's target size and capacity.  ``mode`` forces a
+    decoder through the diagnostic entry (1 one-wave, 2 pipelined, 6 LDS form;
+    7, the group decoder, has no partial form and runs as 1)."""
+    import torch
+    n = int(src_len.numel())
+    if max_cap is None:
+        max_cap = int(dst_cap.max().item()) if n else 0
+    _check_dev(n, src=src, src_off=src_off, src_len=src_len, dst=dst, dst_off=dst_off,
+               dst_cap=dst_cap, ret=ret)
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    args = (_ptr(src), _ptr(src_off), _ptr(src_len), _ptr(dst), _ptr(dst_off), _ptr(dst_cap), _ptr(ret), n,
+            max(0, int(max_cap)), stream)
+    if mode is None:
+        r = lib().lz4e_decompress_partial_batch_dev(*args)
+    else:
+        r = lib().lz4e_debug_decompress_partial(*args, int(mode))
+    if r != 0:
+        raise RuntimeError("lz4e_decompress_partial_batch_dev: " + last_error())
+
+
 PACK_FRAME, PACK_RAW = 0, 1
 
 
@@ -744,6 +812,32 @@ def unpack_batch_dev(packed, pk_off, pk_len, pk_kind, dst, dst_off, dst_cap, ret
                                     _ptr(dst_off), _ptr(dst_cap), _ptr(ret), n, max(0, int(max_cap)), stream)
     if r != 0:
         raise RuntimeError("lz4e_unpack_batch_dev: " + last_error())
+
+
+def unpack_range_batch_dev(packed, pk_off, pk_len, pk_kind, sel, lo, len_, dst, dst_off, ret, max_end: int,
+                           stream=None) -> None:
+    """lz4e_unpack_range_batch_dev on torch tensors (launch only): request j
+    reads bytes [lo[j], lo[j] + len_[j]) of entry sel[j] (``sel`` None: entry
+    j) into dst + dst_off[j].  sel / lo / len_ / ret: int32 tensors, one
+    entry per request (the C ABI reads sel as uint32: an entry number of
+    2^31 or more is its int32 bit pattern); ``max_end`` bounds lo + len_."""
+    import torch
+    n = int(pk_len.numel())
+    nreq = int(lo.numel())
+    # one call: every tensor on one device; the index has n entries, the request arrays nreq
+    _check_dev(0, packed=packed, pk_off=pk_off, pk_len=pk_len, pk_kind=pk_kind, sel=sel, lo=lo, len=len_, dst=dst,
+               dst_off=dst_off, ret=ret)
+    for name, t, need in (("pk_off", pk_off, n + 1), ("pk_len", pk_len, n), ("pk_kind", pk_kind, n), ("sel", sel, nreq),
+                          ("lo", lo, nreq), ("len_", len_, nreq), ("dst_off", dst_off, nreq), ("ret", ret, nreq)):
+        if t is not None and t.numel() < need:
+            raise ValueError(f"{name}: {t.numel()} entries, needs {need}")
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    r = lib().lz4e_unpack_range_batch_dev(_ptr(packed), _ptr(pk_off), _ptr(pk_len), _ptr(pk_kind), n, _ptr(sel),
+                                          _ptr(lo), _ptr(len_), _ptr(dst), _ptr(dst_off), _ptr(ret), nreq,
+                                          max(0, int(max_end)), stream)
+    if r != 0:
+        raise RuntimeError("lz4e_unpack_range_batch_dev: " + last_error())
 
 
 UNPACK_BAD_CRC = -2147483647  # LZ4E_UNPACK_BAD_CRC (INT32_MIN + 1)

@@ -35,6 +35,17 @@ extern "C" int emu_decompress_batch(const uint8_t* src, const uint64_t* src_off,
                                      dict_len, lz4e::kDecWave);
 }
 
+// A partial launch: dst_cap[i] is block i's target size (no dictionary).
+// mode: 0 auto, 1 one-wave decoder, 2 pipelined decoder, 6 LDS form.
+extern "C" int emu_decompress_partial_mode(const uint8_t* src, const uint64_t* src_off,
+                                           const int32_t* src_len, uint8_t* dst, const uint64_t* dst_off,
+                                           const int32_t* target, int32_t* ret, uint32_t nblocks,
+                                           uint32_t max_cap, uint32_t mode) {
+    lz4e::DecompressBatch a{src, src_off, src_len, dst, dst_off, target, ret, nblocks, max_cap, mode};
+    a.partial = true;
+    return lz4e::launch_decompress(a, nullptr) == hipSuccess ? 0 : -1;
+}
+
 // The host entry points' reading of a batch's return values
 // (csrc/lz4e_results.h): number of blocks with ret >= 0, or -1 with the
 // error text when the decoder's watchdog fired on a block.

@@ -25,6 +25,11 @@
 // A leading "--ring N" gives the compressor N record slots per block for its
 // deferred emit (LZ4E_COMPRESS_RECORDS; 0: none, every block emits inline;
 // default: the library's).
+// A leading "--partial T1,T2,..." (with -d, -p or -l; refused with -g / -G,
+// the group decoder has no partial form) decodes the frame once per listed
+// target size in this one process, as a partial decode: each output is an
+// allocation of exactly the target's size, CAPACITY is not used, every decode
+// prints "target T ret R" and writes OUT_FILE.T when R > 0.
 // A leading "--hbm" compresses through the HBM-image kernel whatever the
 // block's size (the batch's max_len is then one byte above the 4 096-byte
 // staging limit at least): two waves per block, a parser and a flusher, for
@@ -33,6 +38,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <string>
 #include <vector>
 
 #if defined(__has_feature)
@@ -50,6 +56,7 @@
 static unsigned g_src_skew = 0, g_dst_skew = 0;
 static bool g_skewed = false;  // without --skew the buffers start at the heap block's start
 static bool g_hbm = false;     // --hbm
+static std::vector<int32_t> g_partial;  // --partial: the targets
 
 // `size` bytes whose byte `lead` sits `skew` bytes past a 16-byte boundary.
 // The heap block ends at the region's end (input: rounded up to the aligned
@@ -105,6 +112,45 @@ extern "C" int emu_decompress_batch_mode(const uint8_t* src, const uint64_t* src
                                          const int32_t* dst_cap, int32_t* ret, uint32_t nblocks,
                                          const int32_t* dict_len, uint32_t mode);
 
+extern "C" int emu_decompress_partial_mode(const uint8_t* src, const uint64_t* src_off,
+                                           const int32_t* src_len, uint8_t* dst, const uint64_t* dst_off,
+                                           const int32_t* target, int32_t* ret, uint32_t nblocks,
+                                           uint32_t max_cap, uint32_t mode);
+
+// Partial decodes of one frame: an exactly sized output per target.
+static int partial_main(int argc, char** argv) {
+    const char m = argv[1][1];
+    if (m == 'g' || m == 'G') {
+        fprintf(stderr, "emu_main: --partial with -%c: the group decoder has no partial form\n", m);
+        return 2;
+    }
+    const uint32_t mode = m == 'p' ? 2u : (m == 'l' ? 6u : 1u);
+    std::vector<uint8_t> frame = slurp(argv[2]);
+    const int32_t csize = (int32_t)frame.size();
+    Skewed in(frame.empty() ? 1 : frame.size(), 0, g_src_skew, true);
+    if (!frame.empty()) memcpy(in.p, frame.data(), frame.size());
+    for (const int32_t target : g_partial) {
+        Skewed out((size_t)target, 0, g_dst_skew, false);
+        const uint64_t so = 0, doff = 0;
+        int32_t ret = -7777;
+        emu_decompress_partial_mode(in.p, &so, &csize, out.p, &doff, &target, &ret, 1, (uint32_t)target, mode);
+        if (!out.ok() || !in.ok()) {
+            fprintf(stderr, "emu_main: a store in front of a buffer (target %d)\n", target);
+            return 3;
+        }
+        printf("target %d ret %d\n", target, ret);
+        if (ret > target) return 3;
+        if (argc > 4 && ret > 0) {
+            const std::string path = std::string(argv[4]) + "." + std::to_string(target);
+            FILE* o = fopen(path.c_str(), "wb");
+            if (!o) return 2;
+            fwrite(out.p, 1, (size_t)ret, o);
+            fclose(o);
+        }
+    }
+    return 0;
+}
+
 // Decode: the frame in an exactly sized buffer, the output buffer exactly
 // [dictionary (last <= 64 KiB) | capacity] -- ASan sees any read before the
 // dictionary or any write past the capacity.
@@ -147,7 +193,7 @@ static int decode_main(int argc, char** argv) {
 int main(int argc, char** argv) {
     long cap_arg = -1;
     while (argc > 2 && (!strcmp(argv[1], "--skew") || !strcmp(argv[1], "--cap") || !strcmp(argv[1], "--ring") ||
-                        !strcmp(argv[1], "--hbm"))) {
+                        !strcmp(argv[1], "--hbm") || !strcmp(argv[1], "--partial"))) {
         if (!strcmp(argv[1], "--hbm")) {
             g_hbm = true;
             argv[1] = argv[0];
@@ -155,7 +201,16 @@ int main(int argc, char** argv) {
             argc -= 1;
             continue;
         }
-        if (!strcmp(argv[1], "--ring")) {
+        if (!strcmp(argv[1], "--partial")) {
+            for (const char* q = argv[2]; *q;) {
+                char* end = nullptr;
+                const long t = strtol(q, &end, 10);
+                if (end == q || t < 0 || t > 0x7FFFFFFFL || (*end && *end != ',')) return 2;
+                g_partial.push_back((int32_t)t);
+                q = *end ? end + 1 : end;
+            }
+            if (g_partial.empty()) return 2;
+        } else if (!strcmp(argv[1], "--ring")) {
             char* end = nullptr;
             const long ring = strtol(argv[2], &end, 10);
             if (!*argv[2] || *end || ring < 0 || ring > 4096) return 2;
@@ -175,7 +230,8 @@ int main(int argc, char** argv) {
     }
     if (argc > 3 && argv[1][0] == '-' &&
         (argv[1][1] == 'd' || argv[1][1] == 'p' || argv[1][1] == 'l' || argv[1][1] == 'g' || argv[1][1] == 'G'))
-        return decode_main(argc, argv);
+        return g_partial.empty() ? decode_main(argc, argv) : partial_main(argc, argv);
+    if (!g_partial.empty()) return 2;  // --partial is a decode option
     if (argc < 3) {
         fprintf(stderr, "usage: emu_main [--skew S,D] [--cap N] [--ring N] [--hbm] BLOCK_FILE TABLE_CLASS [FRAME_OUT [DICT_FILE]]\n");
         return 2;

@@ -5,6 +5,10 @@
 // kernel files (the decoders that run between the two unpack kernels are
 // emu_main's business).  Stand-alone (its own main): built by
 // EMU_PACK=1 build.sh, run by tests/test_emulator_pack.py under ASan + UBSan.
+// `emu_pack range` runs the range read's two kernels instead
+// (range_gather_kernel, range_deliver_kernel; tests/test_emulator_partial.py):
+// the partial launch between them is played by the program, which fills the
+// scratch slots and the decode values itself.
 //
 // The kernels work on the CALLER's memory at byte granularity.  So every
 // frame slot, every source block, `packed`, every unpack destination and
@@ -347,6 +351,149 @@ void unpack_case(const char* what, const std::vector<UEntry>& es, uint32_t packe
     CHECK(packed.canary_ok(), "%s: packed canary", what);
 }
 
+struct RReq {
+    uint32_t sel;
+    int32_t lo, len;
+    uint32_t dst_align;
+    int32_t decoded;  // frame entries: what the partial decode returns for the target (kAsTarget: min(data, target))
+};
+constexpr int32_t kAsTarget = 0x7FFFFFFF;
+
+// range_gather_kernel and range_deliver_kernel on an image of the given
+// entries (UEntry::cap: the bytes a frame entry decodes to).  Every
+// destination is an allocation of exactly the bytes the request must get.
+void range_case(const char* what, const std::vector<UEntry>& es, const std::vector<RReq>& rq, bool with_sel,
+                uint32_t packed_align) {
+    const uint32_t n = (uint32_t)es.size(), m = (uint32_t)rq.size();
+    constexpr int32_t kUntouched = -7777;
+    Buf pk_off(0, 8 * ((size_t)n + 1)), pk_len(0, 4 * (size_t)n), pk_kind(0, n);
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        pk_off.as<uint64_t>()[i] = at;
+        at += (uint64_t)(es[i].len > 0 ? es[i].len : 0);
+        pk_len.as<int32_t>()[i] = es[i].len;
+        pk_kind.as<uint8_t>()[i] = es[i].kind;
+    }
+    pk_off.as<uint64_t>()[n] = at;
+    Buf packed(packed_align, at);
+    packed.fill_random();
+    uint32_t max_end = 0;
+    for (const RReq& q : rq)
+        if (q.lo >= 0 && q.len >= 0 && (uint32_t)q.lo + (uint32_t)q.len > max_end) max_end = (uint32_t)q.lo + (uint32_t)q.len;
+    const uint64_t slot = ((uint64_t)max_end + 15) & ~15ull;
+    Buf sel(0, 4 * (size_t)m), lo(0, 4 * (size_t)m), len(0, 4 * (size_t)m), dst_off(0, 8 * (size_t)m), ret(0, 4 * (size_t)m);
+    Buf g_off(0, 8 * (size_t)m), s_off(0, 8 * (size_t)m), g_len(0, 4 * (size_t)m), g_tgt(0, 4 * (size_t)m),
+        g_ret(0, 4 * (size_t)m), scratch(0, slot * m);
+    scratch.fill_random();
+    // ---- the restatement ----
+    std::vector<int32_t> want(m);
+    std::vector<const uint8_t*> from(m, nullptr);
+    for (uint32_t j = 0; j < m; ++j) {
+        const RReq& q = rq[j];
+        const uint32_t e = with_sel ? q.sel : j;
+        sel.as<uint32_t>()[j] = q.sel;
+        lo.as<int32_t>()[j] = q.lo;
+        len.as<int32_t>()[j] = q.len;
+        ret.as<int32_t>()[j] = kUntouched;
+        g_ret.as<int32_t>()[j] = kUntouched;
+        const bool valid = e < n && q.lo >= 0 && q.len >= 0 && (es[e].kind == LZ4E_PACK_FRAME || es[e].kind == LZ4E_PACK_RAW) &&
+                           es[e].len >= 0;
+        if (!valid) {
+            want[j] = -1;
+        } else if (q.len == 0) {
+            want[j] = 0;
+        } else {
+            const int32_t end = q.lo + q.len;
+            int32_t d;
+            if (es[e].kind == LZ4E_PACK_FRAME) {
+                d = q.decoded == kAsTarget ? (es[e].cap < end ? es[e].cap : end) : q.decoded;
+                g_ret.as<int32_t>()[j] = d;  // the partial launch's value
+                from[j] = scratch.p + j * slot;
+            } else {
+                d = es[e].len < end ? es[e].len : end;
+                from[j] = packed.p + pk_off.as<uint64_t>()[e];
+            }
+            want[j] = d < 0 ? d : (d > q.lo ? d - q.lo : 0);
+        }
+    }
+    std::vector<BufP> dsts;
+    for (uint32_t j = 0; j < m; ++j) {
+        dsts.emplace_back(new Buf(rq[j].dst_align, want[j] > 0 ? (size_t)want[j] : 0));
+        dsts[j]->fill(kFill);
+    }
+    uint8_t* dst = m ? const_cast<uint8_t*>(lowest(dsts)) : nullptr;
+    for (uint32_t j = 0; j < m; ++j) dst_off.as<uint64_t>()[j] = (uint64_t)(dsts[j]->p - dst);
+    // ---- the kernels ----
+    const lz4e::RangeBatch a{packed.p, pk_off.as<uint64_t>(), pk_len.as<int32_t>(), pk_kind.as<uint8_t>(), n,
+                             with_sel ? sel.as<uint32_t>() : nullptr, lo.as<int32_t>(), len.as<int32_t>(), dst,
+                             dst_off.as<uint64_t>(), ret.as<int32_t>(), m, max_end, slot, scratch.p,
+                             g_off.as<uint64_t>(), g_len.as<int32_t>(), g_tgt.as<int32_t>(), s_off.as<uint64_t>(),
+                             g_ret.as<int32_t>()};
+    CHECK(lz4e::launch_range_gather(a, nullptr) == hipSuccess, "%s: gather launch", what);
+    for (uint32_t j = 0; j < m; ++j) {
+        const uint32_t e = with_sel ? rq[j].sel : j;
+        const bool dec = want[j] != -1 && rq[j].len > 0 && e < n && es[e].kind == LZ4E_PACK_FRAME;
+        CHECK(g_off.as<uint64_t>()[j] == (dec ? pk_off.as<uint64_t>()[e] : 0) &&
+                  g_len.as<int32_t>()[j] == (dec ? es[e].len : 0) &&
+                  g_tgt.as<int32_t>()[j] == (dec ? rq[j].lo + rq[j].len : 0) && s_off.as<uint64_t>()[j] == j * slot,
+              "%s: descriptors of request %u", what, j);
+    }
+    CHECK(lz4e::launch_range_deliver(a, nullptr) == hipSuccess, "%s: deliver launch", what);
+    for (uint32_t j = 0; j < m; ++j) {
+        const int32_t r = ret.as<int32_t>()[j];
+        bool good = r == want[j];
+        if (good && r > 0) good = memcmp(dsts[j]->p, from[j] + rq[j].lo, (size_t)r) == 0;
+        CHECK(good, "%s: request %u (sel %u, lo %d, len %d, dst at %u mod 16): ret %d, want %d", what, j, rq[j].sel,
+              rq[j].lo, rq[j].len, rq[j].dst_align, r, want[j]);
+        CHECK(dsts[j]->canary_ok(), "%s: bytes before destination %u written", what, j);
+    }
+    CHECK(packed.canary_ok(), "%s: packed canary", what);
+}
+
+int range_main() {
+    // entries: a frame of 300 bytes that decodes to 1000, a raw entry of 777 bytes, an empty raw entry, an
+    // unknown kind, a negative length, a frame that decodes to 40 bytes
+    const std::vector<UEntry> es = {{LZ4E_PACK_FRAME, 300, 1000, 0}, {LZ4E_PACK_RAW, 777, 0, 0}, {LZ4E_PACK_RAW, 0, 0, 0},
+                                    {7, 50, 50, 0},                   {LZ4E_PACK_RAW, -4, 0, 0},  {LZ4E_PACK_FRAME, 33, 40, 0}};
+    for (uint32_t pa : {0u, 5u, 11u}) {
+        // lo and len at every residue pair mod 16, one entry of each kind, destinations at every residue
+        for (uint32_t e : {0u, 1u}) {
+            std::vector<RReq> rq;
+            for (int32_t lo = 0; lo < 16; ++lo)
+                for (int32_t ln = 0; ln < 16; ++ln) {
+                    rq.push_back({e, lo + 16 * (ln & 3), ln, (uint32_t)(lo * 5 + ln) & 15, kAsTarget});
+                    rq.push_back({e, lo, ln + 16 * (1 + (lo & 7)), (uint32_t)(lo + 3 * ln) & 15, kAsTarget});
+                }
+            range_case("residues", es, rq, true, pa);
+        }
+        // around the entry's end, past it, errors of the decode, invalid requests, repeated and permuted sel
+        std::vector<RReq> rq;
+        for (uint32_t e : {0u, 1u, 5u}) {
+            const int32_t n = es[e].kind == LZ4E_PACK_FRAME ? es[e].cap : es[e].len;
+            for (int32_t lo : {0, 1, n / 2, n - 1, n, n + 5})
+                for (int32_t ln : {0, 1, 17, n, n + 9}) rq.push_back({e, lo, ln, (uint32_t)(lo + ln) & 15, kAsTarget});
+        }
+        rq.push_back({0, 10, 100, 3, -57});            // a damaged frame: the decode's error code
+        rq.push_back({0, 900, 200, 3, 950});           // a decode that ends before the target
+        rq.push_back({0, 990, 10, 3, 500});            // ... and before lo
+        for (uint32_t e : {2u, 3u, 4u, 6u, 0xFFFFFFFFu}) rq.push_back({e, 0, 16, 1, kAsTarget});
+        rq.push_back({1, -1, 16, 1, kAsTarget});
+        rq.push_back({1, 3, -16, 1, kAsTarget});
+        rq.push_back({3, 0, 0, 1, kAsTarget});         // invalid comes before empty
+        range_case("edges", es, rq, true, pa);
+        std::vector<RReq> id;                          // sel == NULL: request j reads entry j
+        for (uint32_t j = 0; j < 8; ++j) id.push_back({99, (int32_t)j, 20, j, kAsTarget});
+        range_case("null sel", es, id, false, pa);
+    }
+    range_case("no request", es, {}, true, 0);
+    if (g_failures) {
+        fprintf(stderr, "emu_pack range: %d failures\n", g_failures);
+        return 1;
+    }
+    printf("emu_pack range ok\n");
+    return 0;
+}
+
 const uint32_t kLens[] = {0, 1, 15, 16, 17, 31, 33, 511, 512, 4096, 4097, 70000};
 constexpr uint32_t kSmallLens = 7;  // 0 ... 33
 
@@ -356,7 +503,8 @@ Entry entry_of(uint32_t len, bool frame, uint32_t sa, uint32_t fa) {
 
 }  // namespace
 
-int main() {
+int main(int argc, char** argv) {
+    if (argc > 1 && !strcmp(argv[1], "range")) return range_main();
     const uint32_t T = lz4e::kPackTile;
     // ---- pack: every source residue against every packed residue, lengths up to 33 ----
     // align 1; ahead of each entry a raw filler whose length puts it at the wanted residue

@@ -42,7 +42,7 @@ struct dim3 {
     dim3(uint32_t a = 1, uint32_t b = 1, uint32_t c = 1) : x(a), y(b), z(c) {}
 };
 typedef int hipError_t;
-enum { hipSuccess = 0, hipErrorOutOfMemory = 2 };
+enum { hipSuccess = 0, hipErrorInvalidValue = 1, hipErrorOutOfMemory = 2 };
 typedef void* hipStream_t;
 inline hipError_t hipGetLastError() { return hipSuccess; }
 inline hipError_t hipMalloc(void**, size_t) { return hipErrorOutOfMemory; }
@@ -233,7 +233,20 @@ inline void emu_sleep() {
 // ---- atomics --------------------------------------------------------------
 #define __HIP_MEMORY_SCOPE_WORKGROUP 0
 #define __hip_atomic_load(p, order, scope) __atomic_load_n(p, order)
-#define __hip_atomic_store(p, v, order, scope) __atomic_store_n(p, v, order)
+// A store by every lane of a wave (lds_release, hs_release: the only users,
+// both behind a lockstep) is ONE store on the GPU.  Here the lanes are
+// threads: a lane descheduled between the lockstep and its own store would
+// write its value later, over a newer one that another wave has stored since
+// -- the pipelined decoder's in-order counters (`stored`, `resolved`) then
+// step backwards and every wait on them stands still (seen with several
+// 256-thread processes sharing the CPUs).  So lane 0 stores for the wave and
+// the others leave once it has.
+template <class T, class V>
+inline void emu_wave_store(T* p, V v, int order) {
+    if ((g_emu_lane & 63) == 0) __atomic_store_n(p, (T)v, order);
+    emu_wave_barrier();
+}
+#define __hip_atomic_store(p, v, order, scope) emu_wave_store(p, v, order)
 #define __hip_atomic_fetch_add(p, v, order, scope) __atomic_fetch_add(p, v, order)
 #define __hip_atomic_fetch_and(p, v, order, scope) __atomic_fetch_and(p, v, order)
 #define __hip_atomic_fetch_or(p, v, order, scope) __atomic_fetch_or(p, v, order)
