@@ -612,7 +612,9 @@ int lz4e_unpack_batch_dev(const uint8_t *packed, const uint64_t *pk_off,
  * scratch for its whole prefix, so for reads far into large entries
  * lz4e_unpack_batch_dev may be the better call.  If the pool refuses it the
  * call returns -1 with lz4e_last_error() set and nothing is launched.
- * The checksum column is not consulted (no verified range read).
+ * The checksum column is not consulted: the range read that checks each
+ * named entry against pk_crc first is lz4e_unpack_range_verified_batch_dev,
+ * below.
  * Returns 0 on successful launches, -22 for max_end above the limit.
  */
 int lz4e_unpack_range_batch_dev(const uint8_t *packed, const uint64_t *pk_off,
@@ -677,6 +679,55 @@ int lz4e_unpack_range_batch_dev(const uint8_t *packed, const uint64_t *pk_off,
  * LZ4E_MAX_INPUT_SIZE bytes), and LZ4E_DECODE_ABORTED is INT32_MIN.
  * max_cap bounds dst_cap[] (0 = unknown) as for unpack and also sizes the
  * checksum's teams (a hint there).
+ *
+ * lz4e_unpack_range_verified_batch_dev: lz4e_unpack_range_batch_dev that
+ * checks each entry a request reads against pk_crc first.  All arguments of
+ * the range read keep their meaning; pk_crc is the column
+ * lz4e_pack_crc_batch_dev wrote.  Per request j, in this order:
+ *   1. invalid, by exactly the range read's test (sel[j] >= nentries, an
+ *      unknown pk_kind, a negative pk_len, a negative lo[j] or len[j]):
+ *      ret[j] = -1, nothing is written and the entry's bytes are not read.
+ *   2. len[j] == 0: ret[j] = 0, nothing is read or written.  The entry is not
+ *      checked on this request's account, and the request gets 0 even when
+ *      another request of the same call finds the entry damaged.
+ *   3. the CRC-32C of packed[pk_off[e], + pk_len[e]), e = sel[j], differs
+ *      from pk_crc[e]: ret[j] = LZ4E_UNPACK_BAD_CRC for every such request
+ *      that names e, no byte of their destinations is written, and no decoder
+ *      and no copy sees the entry.
+ *   4. otherwise ret[j] and the bytes are exactly those of
+ *      lz4e_unpack_range_batch_dev: the partial decode's error codes,
+ *      LZ4E_DECODE_ABORTED, the decoder choice from max_end and nreq,
+ *      LZ4E_DECOMPRESS_MODE, the max_end clamp, and writes confined to
+ *      [dst_off[j], dst_off[j] + ret[j]).
+ * LZ4E_UNPACK_BAD_CRC still collides with no other value of ret[j]: a count
+ * is >= 0, an invalid request is -1, a decode error is -(ip - src) - 1 >=
+ * -0x7E000001 as above, and LZ4E_DECODE_ABORTED is INT32_MIN.
+ * Two things a composition by hand (lz4e_crc32c_batch_dev on a gathered
+ * sub-index, then the plain range read) does not give:
+ *   once per entry      an entry named by any number of rule-3/4 requests of
+ *            one call is summed once: one of them is elected on the device
+ *            and sums for all.
+ *   only what is named  the image bytes of an entry that no rule-3/4 request
+ *            names are not read.  (The index columns may be read at any
+ *            entry.)
+ * max_len is a sizing hint for the checksum's teams: it bounds pk_len[] of
+ * the named entries; 0 = unknown, read as 256 x 64 as the verified unpack
+ * does.  No result depends on it.
+ * Launches only (no kernel waits on another workgroup; the election is one
+ * atomic compare-and-swap per request, its outcome read only behind the
+ * kernel boundary), legal under stream capture.  Footprint: ONE allocation
+ * from the stream-ordered pool of
+ *   nreq x (roundup(max_end, 16) + 28) + 16      the range read's
+ *   + 16 x nreq                   the checksum's offset, length and result
+ *   + 5 x nentries                the elected request and the shadow kind
+ *   + 4 x P                       P = 0 while a checksum team fits a
+ *                                 workgroup (max_len <= 16 KiB), else
+ *                                 nreq x T / 256, T = the team's threads
+ * bytes (T: about max_len / 64, a power of two up to 16384, fewer for huge
+ * batches).  Returns 0 on successful launches and for nreq == 0 (nothing is
+ * launched), -22 for max_end above 0x7FFFFFF0 (checked before any HIP call),
+ * -1 with lz4e_last_error() set on a HIP failure or when the pool refuses
+ * the scratch (nothing is launched then).
  */
 #define LZ4E_UNPACK_BAD_CRC (-2147483647)   /* INT32_MIN + 1 */
 int lz4e_crc32c_batch_dev(const uint8_t *data, const uint64_t *off,
@@ -693,6 +744,14 @@ int lz4e_unpack_verified_batch_dev(const uint8_t *packed, const uint64_t *pk_off
 				   const uint64_t *dst_off, const int32_t *dst_cap,
 				   int32_t *ret, uint32_t nblocks,
 				   uint32_t max_cap, void *stream);
+int lz4e_unpack_range_verified_batch_dev(const uint8_t *packed, const uint64_t *pk_off,
+					 const int32_t *pk_len, const uint8_t *pk_kind,
+					 const uint32_t *pk_crc, uint32_t nentries,
+					 const uint32_t *sel, const int32_t *lo,
+					 const int32_t *len, uint8_t *dst,
+					 const uint64_t *dst_off, int32_t *ret,
+					 uint32_t nreq, uint32_t max_end,
+					 uint32_t max_len, void *stream);
 
 #ifdef __cplusplus
 }

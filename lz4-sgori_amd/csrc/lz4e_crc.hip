@@ -1,9 +1,10 @@
 // lz4e_crc.hip -- the packed frame store's checksum (gfx950): CRC-32C
 // (Castagnoli: reflected, polynomial 0x1EDC6F41, initial value and final xor
-// 0xFFFFFFFF) of every entry of a batch, for the three entry points of
-// include/lz4e.h that need it: lz4e_crc32c_batch_dev, lz4e_pack_crc_batch_dev
-// and lz4e_unpack_verified_batch_dev.  One kernel serves all three; only
-// where an entry's bytes come from differs (CrcBatch, lz4e_gpu.h).
+// 0xFFFFFFFF) of every entry of a batch, for the four entry points of
+// include/lz4e.h that need it: lz4e_crc32c_batch_dev, lz4e_pack_crc_batch_dev,
+// lz4e_unpack_verified_batch_dev and lz4e_unpack_range_verified_batch_dev.
+// One kernel serves all four; only where an entry's bytes come from differs
+// (CrcBatch, lz4e_gpu.h).
 //
 // The state register is kept reflected: bit 31 is x^0 and "times x" is
 // (b >> 1) ^ (b & 1 ? 0x82F63B78 : 0).  Feeding n zero bytes to a state is a
@@ -41,7 +42,10 @@
 // unpack_verify_mask_kernel and unpack_verify_ret_kernel wrap the unchanged
 // lz4e_unpack_batch_dev composition (lz4e_pack.hip): the first hides every
 // entry that is invalid or whose checksum differs from the decoders and from
-// the raw copy, the second writes their ret.
+// the raw copy, the second writes their ret.  The four range_verify_* kernels
+// wrap the unchanged lz4e_unpack_range_batch_dev composition in the same way
+// for lz4e_unpack_range_verified_batch_dev (lz4e_gpu.h, RangeVerifyBatch): an
+// entry is summed once per call, by the one request elected for it.
 //
 // Kernels and launches only (no other runtime call), so that tools/emu
 // compiles this file as host C++ (tools/emu/emu_crc.cpp,
@@ -50,6 +54,7 @@
 #include <stdint.h>
 
 #include "lz4e_gpu.h"
+#include "lz4e_range.h"
 #include "lz4e_wave.h"
 
 namespace lz4e {
@@ -252,6 +257,62 @@ __global__ __launch_bounds__(256) void unpack_verify_ret_kernel(const uint8_t* _
     else if (show == kVerifyInvalid) ret[i] = -1;
 }
 
+// The verified range read's four kernels (lz4e_gpu.h, RangeVerifyBatch), a
+// thread per request each.  A request's validity is range_req's on the REAL
+// kind column, the plain range read's own test.
+__global__ __launch_bounds__(256) void range_verify_init_kernel(const uint8_t* __restrict__ pk_kind,
+                                                                uint32_t nentries, const uint32_t* __restrict__ sel,
+                                                                uint32_t nreq, uint32_t* __restrict__ owner,
+                                                                uint8_t* __restrict__ shown) {
+    const uint64_t j = (uint64_t)blockIdx.x * kCrcThreads + threadIdx.x;
+    if (j >= nreq) return;
+    const uint32_t e = sel ? sel[j] : (uint32_t)j;
+    if (e >= nentries) return;
+    // (requests that share an entry all store the same two values)
+    owner[e] = kNoOwner;
+    shown[e] = pk_kind[e];
+}
+
+__global__ __launch_bounds__(256) void range_verify_elect_kernel(
+    const uint64_t* __restrict__ pk_off, const int32_t* __restrict__ pk_len, const uint8_t* __restrict__ pk_kind,
+    uint32_t nentries, const uint32_t* __restrict__ sel, const int32_t* __restrict__ lo,
+    const int32_t* __restrict__ len, uint32_t nreq, uint32_t* __restrict__ owner, uint64_t* __restrict__ c_off,
+    int32_t* __restrict__ c_len) {
+    const uint64_t j = (uint64_t)blockIdx.x * kCrcThreads + threadIdx.x;
+    if (j >= nreq) return;
+    const RangeReq q = range_req(sel, lo, len, pk_len, pk_kind, nentries, j);
+    bool won = false;
+    if (q.valid && len[j] > 0) won = atomicCAS(&owner[q.entry], kNoOwner, (uint32_t)j) == kNoOwner;
+    c_off[j] = won ? pk_off[q.entry] : 0;
+    c_len[j] = won ? pk_len[q.entry] : 0;
+}
+
+__global__ __launch_bounds__(256) void range_verify_verdict_kernel(
+    const int32_t* __restrict__ pk_len, const uint8_t* __restrict__ pk_kind, const uint32_t* __restrict__ pk_crc,
+    uint32_t nentries, const uint32_t* __restrict__ sel, const int32_t* __restrict__ lo,
+    const int32_t* __restrict__ len, uint32_t nreq, const uint32_t* __restrict__ owner,
+    const uint32_t* __restrict__ got, uint8_t* __restrict__ shown) {
+    const uint64_t j = (uint64_t)blockIdx.x * kCrcThreads + threadIdx.x;
+    if (j >= nreq) return;
+    const RangeReq q = range_req(sel, lo, len, pk_len, pk_kind, nentries, j);
+    // (only a request that wanted its entry was ever made its owner)
+    if (q.valid && owner[q.entry] == (uint32_t)j && got[j] != pk_crc[q.entry]) shown[q.entry] = (uint8_t)kVerifyBadCrc;
+}
+
+// Behind range_deliver_kernel, which saw `shown` and left -1 for every request
+// on a marked entry.
+__global__ __launch_bounds__(256) void range_verify_ret_kernel(
+    const int32_t* __restrict__ pk_len, const uint8_t* __restrict__ pk_kind, uint32_t nentries,
+    const uint32_t* __restrict__ sel, const int32_t* __restrict__ lo, const int32_t* __restrict__ len,
+    uint32_t nreq, const uint8_t* __restrict__ shown, int32_t* __restrict__ ret) {
+    const uint64_t j = (uint64_t)blockIdx.x * kCrcThreads + threadIdx.x;
+    if (j >= nreq) return;
+    const RangeReq q = range_req(sel, lo, len, pk_len, pk_kind, nentries, j);
+    if (!q.valid) return;
+    if (len[j] == 0) ret[j] = 0;
+    else if (shown[q.entry] == kVerifyBadCrc) ret[j] = kUnpackBadCrc;
+}
+
 dim3 per_entry_grid(uint32_t nblocks) { return dim3((uint32_t)(((uint64_t)nblocks + kCrcThreads - 1) / kCrcThreads)); }
 
 }  // namespace
@@ -300,6 +361,35 @@ hipError_t launch_unpack_verify_ret(const uint8_t* shown, uint32_t nblocks, int3
     if (nblocks == 0) return hipSuccess;
     hipLaunchKernelGGL(unpack_verify_ret_kernel, per_entry_grid(nblocks), dim3(kCrcThreads), 0, stream, shown,
                        nblocks, ret);
+    return hipGetLastError();
+}
+
+hipError_t launch_range_verify_init(const RangeVerifyBatch& a, hipStream_t stream) {
+    if (a.nreq == 0) return hipSuccess;
+    hipLaunchKernelGGL(range_verify_init_kernel, per_entry_grid(a.nreq), dim3(kCrcThreads), 0, stream, a.pk_kind,
+                       a.nentries, a.sel, a.nreq, a.owner, a.shown);
+    return hipGetLastError();
+}
+
+hipError_t launch_range_verify_elect(const RangeVerifyBatch& a, hipStream_t stream) {
+    if (a.nreq == 0) return hipSuccess;
+    hipLaunchKernelGGL(range_verify_elect_kernel, per_entry_grid(a.nreq), dim3(kCrcThreads), 0, stream, a.pk_off,
+                       a.pk_len, a.pk_kind, a.nentries, a.sel, a.lo, a.len, a.nreq, a.owner, a.c_off, a.c_len);
+    return hipGetLastError();
+}
+
+hipError_t launch_range_verify_verdict(const RangeVerifyBatch& a, hipStream_t stream) {
+    if (a.nreq == 0) return hipSuccess;
+    hipLaunchKernelGGL(range_verify_verdict_kernel, per_entry_grid(a.nreq), dim3(kCrcThreads), 0, stream, a.pk_len,
+                       a.pk_kind, a.pk_crc, a.nentries, a.sel, a.lo, a.len, a.nreq, (const uint32_t*)a.owner,
+                       (const uint32_t*)a.got, a.shown);
+    return hipGetLastError();
+}
+
+hipError_t launch_range_verify_ret(const RangeVerifyBatch& a, hipStream_t stream) {
+    if (a.nreq == 0) return hipSuccess;
+    hipLaunchKernelGGL(range_verify_ret_kernel, per_entry_grid(a.nreq), dim3(kCrcThreads), 0, stream, a.pk_len,
+                       a.pk_kind, a.nentries, a.sel, a.lo, a.len, a.nreq, (const uint8_t*)a.shown, a.ret);
     return hipGetLastError();
 }
 

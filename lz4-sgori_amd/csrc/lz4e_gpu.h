@@ -233,4 +233,49 @@ hipError_t launch_unpack_verify_mask(const int32_t* pk_len, const uint8_t* pk_ki
                                      hipStream_t stream);
 hipError_t launch_unpack_verify_ret(const uint8_t* shown, uint32_t nblocks, int32_t* ret, hipStream_t stream);
 
+// The verified range read (include/lz4e.h,
+// lz4e_unpack_range_verified_batch_dev) is lz4e_unpack_range_batch_dev's
+// composition between four thread-per-request kernels and launch_crc.  A
+// request that is valid with len > 0 "wants" its entry.
+//   init     every entry a request names: owner[e] = kNoOwner, shown[e] =
+//            pk_kind[e].  shown is the kind column the range kernels are given.
+//   elect    one wanting request per entry becomes its owner (one atomicCAS on
+//            owner[e]; which one wins changes no result) and describes the
+//            entry to launch_crc, c_off[j] / c_len[j]; every other request
+//            describes 0 bytes, which launch_crc does not read.  So an entry
+//            is summed once however many requests name it, and the bytes of
+//            an entry nobody wants are not read.
+//   launch_crc on (packed, c_off, c_len) over nreq entries -> got[nreq]
+//   verdict  the owner with got[j] != pk_crc[e] sets shown[e] = kVerifyBadCrc:
+//            launch_range_gather and launch_range_deliver, run on shown, take
+//            the entry for one of unknown kind -- no descriptor, no read, no
+//            write, ret -1.
+//   ret      behind launch_range_deliver, by the real pk_kind: 0 for a valid
+//            request with len 0 (deliver has said -1 if its entry was marked),
+//            kUnpackBadCrc for every other valid request on a marked entry.
+// owner / shown have nentries elements (only those named are touched), c_off /
+// c_len / got nreq.
+constexpr uint32_t kNoOwner = 0xFFFFFFFFu;
+struct RangeVerifyBatch {
+    const uint64_t* pk_off;
+    const int32_t* pk_len;
+    const uint8_t* pk_kind;
+    const uint32_t* pk_crc;
+    uint32_t nentries;
+    const uint32_t* sel;  // nullable
+    const int32_t* lo;
+    const int32_t* len;
+    int32_t* ret;
+    uint32_t nreq;
+    uint32_t* owner;
+    uint8_t* shown;
+    uint64_t* c_off;
+    int32_t* c_len;
+    uint32_t* got;
+};
+hipError_t launch_range_verify_init(const RangeVerifyBatch& a, hipStream_t stream);
+hipError_t launch_range_verify_elect(const RangeVerifyBatch& a, hipStream_t stream);
+hipError_t launch_range_verify_verdict(const RangeVerifyBatch& a, hipStream_t stream);
+hipError_t launch_range_verify_ret(const RangeVerifyBatch& a, hipStream_t stream);
+
 }  // namespace lz4e

@@ -1157,6 +1157,61 @@ int lz4e_unpack_verified_batch_dev(const uint8_t* packed, const uint64_t* pk_off
     return ok ? 0 : -1;
 }
 
+// The verified range read: lz4e_unpack_range_batch_dev's three steps, on the
+// shadow kind column `shown`, between the election and checksum in front and
+// the ret kernel behind (lz4e_gpu.h, RangeVerifyBatch).  One allocation: the
+// range read's slots and descriptors, then c_off[nreq] (8-byte words first),
+// c_len[nreq], got[nreq], owner[nentries], partial[words], shown[nentries].
+int lz4e_unpack_range_verified_batch_dev(const uint8_t* packed, const uint64_t* pk_off, const int32_t* pk_len,
+                                         const uint8_t* pk_kind, const uint32_t* pk_crc, uint32_t nentries,
+                                         const uint32_t* sel, const int32_t* lo, const int32_t* len, uint8_t* dst,
+                                         const uint64_t* dst_off, int32_t* ret, uint32_t nreq, uint32_t max_end,
+                                         uint32_t max_len, void* stream) {
+    g_err.clear();
+    if (nreq == 0) return 0;
+    if (max_end > 0x7FFFFFF0u) {
+        set_err("lz4e_unpack_range_verified_batch_dev: max_end above 0x7FFFFFF0");
+        return -22;
+    }
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint32_t hint = max_len ? max_len : 256 * 64;  // unknown: a workgroup per entry
+    const uint64_t words = lz4e::crc_partial_words(hint, nreq);
+    const uint64_t slot = align16((uint64_t)max_end);
+    const uint64_t data = slot * nreq;  // a multiple of 16: the words behind it are aligned
+    uint8_t* scratch = nullptr;
+    if (!hip_ok(hipMallocAsync((void**)&scratch, data + 44ull * nreq + 5ull * nentries + 4 * words + 16, s),
+                "verified range read scratch"))
+        return -1;
+    uint64_t* g_off = reinterpret_cast<uint64_t*>(scratch + data);
+    uint64_t* s_off = g_off + nreq;
+    uint64_t* c_off = s_off + nreq;
+    int32_t* g_len = reinterpret_cast<int32_t*>(c_off + nreq);
+    int32_t* g_tgt = g_len + nreq;
+    int32_t* g_ret = g_tgt + nreq;
+    int32_t* c_len = g_ret + nreq;
+    uint32_t* got = reinterpret_cast<uint32_t*>(c_len + nreq);
+    uint32_t* owner = got + nreq;
+    uint32_t* partial = owner + nentries;
+    uint8_t* shown = reinterpret_cast<uint8_t*>(partial + words);
+    const lz4e::RangeVerifyBatch v{pk_off, pk_len, pk_kind, pk_crc, nentries, sel,   lo,    len,
+                                   ret,    nreq,   owner,   shown,  c_off,    c_len, got};
+    const lz4e::CrcBatch c{packed, c_off, nullptr, nullptr, nullptr, c_len, got, nreq, hint};
+    const lz4e::RangeBatch r{packed, pk_off, pk_len, shown, nentries, sel,   lo,    len,   dst,   dst_off,
+                             ret,    nreq,   max_end, slot,  scratch,  g_off, g_len, g_tgt, s_off, g_ret};
+    lz4e::DecompressBatch d{packed, g_off, g_len, scratch, s_off, g_tgt, g_ret, nreq, max_end};
+    d.partial = true;
+    const bool ok = hip_ok(lz4e::launch_range_verify_init(v, s), "verified range init launch") &&
+                    hip_ok(lz4e::launch_range_verify_elect(v, s), "verified range elect launch") &&
+                    hip_ok(lz4e::launch_crc(c, partial, s), "verified range crc launch") &&
+                    hip_ok(lz4e::launch_range_verify_verdict(v, s), "verified range verdict launch") &&
+                    hip_ok(lz4e::launch_range_gather(r, s), "verified range gather launch") &&
+                    hip_ok(lz4e::launch_decompress(d, s), "verified range decompress launch") &&
+                    hip_ok(lz4e::launch_range_deliver(r, s), "verified range deliver launch") &&
+                    hip_ok(lz4e::launch_range_verify_ret(v, s), "verified range ret launch");
+    (void)hipFreeAsync(scratch, s);
+    return ok ? 0 : -1;
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------

@@ -45,6 +45,7 @@
 
 #include "lz4e_copy.h"
 #include "lz4e_gpu.h"
+#include "lz4e_range.h"
 #include "lz4e_wave.h"
 
 namespace lz4e {
@@ -201,17 +202,7 @@ __global__ __launch_bounds__(256) void unpack_raw_kernel(
 // touch -- not a frame entry, invalid, or empty -- gets length 0 and target 0:
 // each decoder returns for it before it reads or writes anything.  The
 // target is clamped to max_end, the size of a request's scratch slot.
-struct RangeReq {
-    uint32_t entry;
-    bool valid;  // the entry exists, its kind is known, its length and the range are not negative
-};
-LZ4E_DEV RangeReq range_req(const uint32_t* sel, const int32_t* lo, const int32_t* len, const int32_t* pk_len,
-                            const uint8_t* pk_kind, uint32_t nentries, uint64_t j) {
-    const uint32_t e = sel ? sel[j] : (uint32_t)j;
-    bool ok = e < nentries && lo[j] >= 0 && len[j] >= 0;
-    if (ok) ok = (pk_kind[e] == kPackFrame || pk_kind[e] == kPackRaw) && pk_len[e] >= 0;
-    return RangeReq{e, ok};
-}
+// (RangeReq / range_req, a request's validity: lz4e_range.h.)
 LZ4E_DEV int32_t range_end(const int32_t* lo, const int32_t* len, uint32_t max_end, uint64_t j) {
     const uint64_t end = (uint64_t)(uint32_t)lo[j] + (uint32_t)len[j];
     return (int32_t)(end < max_end ? end : max_end);

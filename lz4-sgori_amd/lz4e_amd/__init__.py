@@ -35,7 +35,7 @@ __all__ = [
     "pack_batch_dev", "unpack_batch_dev", "PACK_FRAME", "PACK_RAW",
     "crc32c_batch_dev", "pack_crc_batch_dev", "unpack_verified_batch_dev", "UNPACK_BAD_CRC",
     "decompress_safe_partial", "decompress_partial_batch", "decompress_partial_batch_dev",
-    "unpack_range_batch_dev",
+    "unpack_range_batch_dev", "unpack_range_verified_batch_dev",
 ]
 
 PAGE_SIZE = 4096
@@ -59,7 +59,7 @@ EXPORTED_SYMBOLS = (
     "lz4e_pack_batch_dev", "lz4e_unpack_batch_dev",
     "lz4e_crc32c_batch_dev", "lz4e_pack_crc_batch_dev", "lz4e_unpack_verified_batch_dev",
     "LZ4E_decompress_safe_partial", "lz4e_decompress_partial_batch", "lz4e_decompress_partial_batch_dev",
-    "lz4e_unpack_range_batch_dev",
+    "lz4e_unpack_range_batch_dev", "lz4e_unpack_range_verified_batch_dev",
 )
 
 
@@ -200,6 +200,9 @@ def lib() -> ctypes.CDLL:
         L.lz4e_debug_decompress_partial.restype = I32
         L.lz4e_unpack_range_batch_dev.argtypes = [P] * 4 + [U32] + [P] * 6 + [U32, U32, P]
         L.lz4e_unpack_range_batch_dev.restype = I32
+    if hasattr(L, "lz4e_unpack_range_verified_batch_dev"):
+        L.lz4e_unpack_range_verified_batch_dev.argtypes = [P] * 5 + [U32] + [P] * 6 + [U32, U32, U32, P]
+        L.lz4e_unpack_range_verified_batch_dev.restype = I32
     _lib = L
     return L
 
@@ -882,6 +885,38 @@ def pack_crc_batch_dev(frames, fr_off, src, src_off, pk_len, pk_kind, pk_crc, ma
                                       _ptr(pk_kind), _ptr(pk_crc), n, int(max_len), stream)
     if r != 0:
         raise RuntimeError("lz4e_pack_crc_batch_dev: " + last_error())
+
+
+def unpack_range_verified_batch_dev(packed, pk_off, pk_len, pk_kind, pk_crc, sel, lo, len_, dst, dst_off, ret,
+                                    max_end: int, max_len: Optional[int] = None, stream=None) -> None:
+    """lz4e_unpack_range_verified_batch_dev on torch tensors (launch only):
+    unpack_range_batch_dev that checks each entry a request reads against
+    pk_crc first (once per call, however many requests name it); every
+    request with len_ > 0 on an entry whose stored bytes do not match gets ret
+    UNPACK_BAD_CRC and nothing is written for it.  pk_crc: int32 bit patterns,
+    as pack_crc_batch_dev writes them.  ``max_len`` is a sizing hint that
+    bounds pk_len (default: read from pk_len, which synchronises); no result
+    depends on it."""
+    import torch
+    n = int(pk_len.numel())
+    nreq = int(lo.numel())
+    _check_dev(0, packed=packed, pk_off=pk_off, pk_len=pk_len, pk_kind=pk_kind, pk_crc=pk_crc, sel=sel, lo=lo,
+               len=len_, dst=dst, dst_off=dst_off, ret=ret)
+    for name, t, need in (("pk_off", pk_off, n + 1), ("pk_len", pk_len, n), ("pk_kind", pk_kind, n),
+                          ("pk_crc", pk_crc, n), ("sel", sel, nreq), ("lo", lo, nreq), ("len_", len_, nreq),
+                          ("dst_off", dst_off, nreq), ("ret", ret, nreq)):
+        if t is not None and t.numel() < need:
+            raise ValueError(f"{name}: {t.numel()} entries, needs {need}")
+    if max_len is None:
+        max_len = max(0, int(pk_len.max().item())) if n else 0
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    r = lib().lz4e_unpack_range_verified_batch_dev(_ptr(packed), _ptr(pk_off), _ptr(pk_len), _ptr(pk_kind),
+                                                   _ptr(pk_crc), n, _ptr(sel), _ptr(lo), _ptr(len_), _ptr(dst),
+                                                   _ptr(dst_off), _ptr(ret), nreq, max(0, int(max_end)),
+                                                   max(0, int(max_len)), stream)
+    if r != 0:
+        raise RuntimeError("lz4e_unpack_range_verified_batch_dev: " + last_error())
 
 
 def unpack_verified_batch_dev(packed, pk_off, pk_len, pk_kind, pk_crc, dst, dst_off, dst_cap, ret, stream=None,

@@ -7,7 +7,10 @@
 // emu_main's business: here their part is played by a stand-in that returns
 // -1 for a masked length of 0 and a marker otherwise).  Stand-alone (its own
 // main): built by EMU_CRC=1 build.sh, run by tests/test_emulator_crc.py under
-// ASan + UBSan.
+// ASan + UBSan.  `emu_crc rangev` runs, in place of all that, the verified
+// range read's composition (rangev_case: the four range_verify_* kernels of
+// lz4e_crc.hip around launch_crc and lz4e_pack.hip's range_gather_kernel and
+// range_deliver_kernel; tests/test_emulator_range_verified.py).
 //
 // The kernels read the CALLER's memory at byte granularity.  So every entry
 // here is its own heap allocation that ends exactly at its last byte (ASan's
@@ -26,6 +29,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <memory>
 #include <thread>
 #include <vector>
@@ -394,9 +398,262 @@ void verify_case(const char* what, const std::vector<VEntry>& es, uint32_t packe
 const int32_t kLens[] = {0, 1, 3, 4, 5, 15, 16, 17, 31, 33, 63, 64, 65, 511, 512, 4096, 4097, 70000};
 constexpr uint32_t kSmallLens = 13;  // 0 ... 65
 
+// ---- the verified range read (`emu_crc rangev`) ----
+enum Damage { kClean, kWrongCrc, kFlipFirst, kFlipLast };
+struct REntry {
+    uint8_t kind;
+    int32_t len;
+    Damage damage;
+    bool outside;  // pk_off points outside every allocation: the entry must not be read
+};
+struct RReq {
+    uint32_t sel;
+    int32_t lo, len;
+};
+
+// lz4e_unpack_range_verified_batch_dev's composition, launch for launch as
+// lz4e_host.hip issues it, once per hint.  Every entry is an allocation of its
+// own (exactly pk_len bytes), every scratch array one of exactly the size the
+// header states, every destination one of exactly the bytes its request must
+// get.  The decoders' part is played by a stand-in that takes a frame's bytes
+// for its data: -1 for a length of 0 before it reads or writes anything, else
+// the first min(length, target) bytes into the request's slot.  Expected
+// values: ref_crc and the plain loop below.
+void rangev_case(const char* what, const std::vector<REntry>& es, const std::vector<RReq>& rq, bool null_sel,
+                 uint32_t max_end, const std::vector<uint32_t>& hints) {
+    const uint32_t n = (uint32_t)es.size(), m = (uint32_t)rq.size();
+    std::vector<BufP> ents;
+    for (uint32_t i = 0; i < n; ++i) {
+        ents.emplace_back(new Buf(i * 7 + 1, !es[i].outside && es[i].len > 0 ? (size_t)es[i].len : 0));
+        ents[i]->fill_random();
+    }
+    const uint8_t* packed = lowest(ents);
+    Buf pk_off(0, 8 * ((size_t)n + 1)), pk_len(0, 4 * (size_t)n), pk_kind(0, n), pk_crc(0, 4 * (size_t)n);
+    std::vector<bool> damaged(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const REntry& e = es[i];
+        pk_off.as<uint64_t>()[i] = e.outside ? ((uint64_t)1 << 46) + i : (uint64_t)(ents[i]->p - packed);
+        pk_len.as<int32_t>()[i] = e.len;
+        pk_kind.as<uint8_t>()[i] = e.kind;
+        uint32_t c = e.outside ? 0x1234567u : ref_crc(ents[i]->p, ents[i]->n);
+        damaged[i] = e.damage != kClean;
+        if (e.damage == kWrongCrc || ents[i]->n == 0) {
+            if (damaged[i]) c ^= 1u << (i % 32);
+        } else if (e.damage == kFlipFirst) {
+            ents[i]->p[0] ^= 0x01;
+        } else if (e.damage == kFlipLast) {
+            ents[i]->p[ents[i]->n - 1] ^= 0x80;
+        }
+        pk_crc.as<uint32_t>()[i] = c;
+    }
+    pk_off.as<uint64_t>()[n] = 0;
+    // the requests and what each must get
+    Buf sel(0, 4 * (size_t)m), lo(0, 4 * (size_t)m), len(0, 4 * (size_t)m);
+    std::vector<int32_t> want(m);
+    std::vector<int64_t> count(m);  // bytes delivered; -1: rule 1, -2: rule 2, -3: rule 3
+    std::vector<bool> wanted(n);
+    for (uint32_t j = 0; j < m; ++j) {
+        const RReq& q = rq[j];
+        if (null_sel && q.sel != j) abort();
+        sel.as<uint32_t>()[j] = q.sel;
+        lo.as<int32_t>()[j] = q.lo;
+        len.as<int32_t>()[j] = q.len;
+        const bool valid = q.sel < n && q.lo >= 0 && q.len >= 0 &&
+                           (es[q.sel].kind == LZ4E_PACK_FRAME || es[q.sel].kind == LZ4E_PACK_RAW) && es[q.sel].len >= 0;
+        if (!valid) {
+            want[j] = -1, count[j] = -1;
+        } else if (q.len == 0) {
+            want[j] = 0, count[j] = -2;
+        } else {
+            const REntry& e = es[q.sel];
+            if (e.outside) abort();  // a mistake in the case: this request reads the entry
+            wanted[q.sel] = true;
+            const uint64_t end = std::min<uint64_t>((uint64_t)q.lo + (uint64_t)q.len, max_end);
+            const int64_t d = (int64_t)std::min<uint64_t>((uint64_t)e.len, end);
+            const int64_t cnt = e.kind == LZ4E_PACK_FRAME && e.len == 0 ? -1 : d > q.lo ? d - q.lo : 0;
+            if (damaged[q.sel]) want[j] = LZ4E_UNPACK_BAD_CRC, count[j] = -3;
+            else want[j] = (int32_t)cnt, count[j] = cnt < 0 ? 0 : cnt;
+        }
+    }
+    uint32_t nwanted = 0;
+    for (uint32_t i = 0; i < n; ++i) nwanted += wanted[i];
+    const uint64_t slot = ((uint64_t)max_end + 15) & ~(uint64_t)15;
+    for (uint32_t hint : hints) {
+        std::vector<BufP> dsts;
+        for (uint32_t j = 0; j < m; ++j) {
+            // a refused request's slot is what a plain read might have written
+            const size_t sz = count[j] >= 0 ? (size_t)count[j] : (size_t)std::min<int64_t>(std::max(rq[j].len, 0), 512);
+            dsts.emplace_back(new Buf(j * 3 + 2, sz));
+            dsts[j]->fill(kFill);
+        }
+        uint8_t* dst = const_cast<uint8_t*>(lowest(dsts));
+        Buf dst_off(0, 8 * (size_t)m), ret(0, 4 * (size_t)m);
+        for (uint32_t j = 0; j < m; ++j) dst_off.as<uint64_t>()[j] = (uint64_t)(dsts[j]->p - dst);
+        const uint64_t words = lz4e::crc_partial_words(hint, m);
+        Buf slots(0, (size_t)(slot * m)), g_off(0, 8 * (size_t)m), s_off(0, 8 * (size_t)m), c_off(0, 8 * (size_t)m),
+            g_len(0, 4 * (size_t)m), g_tgt(0, 4 * (size_t)m), g_ret(0, 4 * (size_t)m), c_len(0, 4 * (size_t)m),
+            got(0, 4 * (size_t)m), owner(0, 4 * (size_t)n), partial(0, 4 * (size_t)words), shown(0, n);
+        for (Buf* b : {&ret, &slots, &g_off, &s_off, &c_off, &g_len, &g_tgt, &g_ret, &c_len, &got, &owner, &partial, &shown})
+            b->fill(kFill);
+        const uint32_t* selp = null_sel ? nullptr : sel.as<uint32_t>();
+        const lz4e::RangeVerifyBatch v{pk_off.as<uint64_t>(), pk_len.as<int32_t>(), pk_kind.as<uint8_t>(),
+                                       pk_crc.as<uint32_t>(), n, selp, lo.as<int32_t>(), len.as<int32_t>(),
+                                       ret.as<int32_t>(), m, owner.as<uint32_t>(), shown.as<uint8_t>(),
+                                       c_off.as<uint64_t>(), c_len.as<int32_t>(), got.as<uint32_t>()};
+        const lz4e::CrcBatch c{packed, c_off.as<uint64_t>(), nullptr, nullptr, nullptr, c_len.as<int32_t>(),
+                               got.as<uint32_t>(), m, hint};
+        const lz4e::RangeBatch r{packed, pk_off.as<uint64_t>(), pk_len.as<int32_t>(), shown.as<uint8_t>(), n, selp,
+                                 lo.as<int32_t>(), len.as<int32_t>(), dst, dst_off.as<uint64_t>(), ret.as<int32_t>(), m,
+                                 max_end, slot, slots.p, g_off.as<uint64_t>(), g_len.as<int32_t>(), g_tgt.as<int32_t>(),
+                                 s_off.as<uint64_t>(), g_ret.as<int32_t>()};
+        CHECK(lz4e::launch_range_verify_init(v, nullptr) == hipSuccess, "%s: init launch", what);
+        CHECK(lz4e::launch_range_verify_elect(v, nullptr) == hipSuccess, "%s: elect launch", what);
+        CHECK(lz4e::launch_crc(c, words ? partial.as<uint32_t>() : nullptr, nullptr) == hipSuccess, "%s: crc launch", what);
+        CHECK(lz4e::launch_range_verify_verdict(v, nullptr) == hipSuccess, "%s: verdict launch", what);
+        CHECK(lz4e::launch_range_gather(r, nullptr) == hipSuccess, "%s: gather launch", what);
+        for (uint32_t j = 0; j < m; ++j) {  // the decoders
+            const int32_t fl = g_len.as<int32_t>()[j], tgt = g_tgt.as<int32_t>()[j];
+            if (fl == 0) {
+                g_ret.as<int32_t>()[j] = -1;
+                continue;
+            }
+            const int32_t d = fl < tgt ? fl : tgt;
+            memcpy(slots.p + s_off.as<uint64_t>()[j], packed + g_off.as<uint64_t>()[j], (size_t)d);
+            g_ret.as<int32_t>()[j] = d;
+        }
+        CHECK(lz4e::launch_range_deliver(r, nullptr) == hipSuccess, "%s: deliver launch", what);
+        CHECK(lz4e::launch_range_verify_ret(v, nullptr) == hipSuccess, "%s: ret launch", what);
+        // once per entry: one owner per wanted entry describes it to the checksum, nobody else describes anything
+        uint32_t nowners = 0;
+        for (uint32_t j = 0; j < m; ++j) {
+            const bool owns = count[j] != -1 && count[j] != -2 && owner.as<uint32_t>()[rq[j].sel] == j;
+            nowners += owns;
+            const int32_t cl = c_len.as<int32_t>()[j];
+            CHECK(cl == (owns ? es[rq[j].sel].len : 0), "%s: hint %u, request %u describes %d bytes to the checksum", what, hint,
+                  j, cl);
+        }
+        CHECK(nowners == nwanted, "%s: hint %u: %u owners for %u wanted entries", what, hint, nowners, nwanted);
+        for (uint32_t j = 0; j < m; ++j) {
+            const int32_t rr = ret.as<int32_t>()[j];
+            bool good = rr == want[j];
+            if (count[j] > 0) good &= memcmp(dsts[j]->p, ents[rq[j].sel]->p + rq[j].lo, (size_t)count[j]) == 0;
+            else good &= dsts[j]->all(kFill);
+            CHECK(good, "%s: hint %u, request %u of %u (entry %u, lo %d, len %d; kind %u, len %d, damage %d): ret %d, expected %d%s",
+                  what, hint, j, m, rq[j].sel, rq[j].lo, rq[j].len, rq[j].sel < n ? es[rq[j].sel].kind : 999,
+                  rq[j].sel < n ? es[rq[j].sel].len : -999, rq[j].sel < n ? (int)es[rq[j].sel].damage : -1, rr, want[j],
+                  rr == want[j] ? ", wrong bytes" : "");
+            CHECK(dsts[j]->canary_ok(), "%s: bytes before destination %u written", what, j);
+        }
+    }
+    for (uint32_t i = 0; i < n; ++i) CHECK(ents[i]->canary_ok(), "%s: canary of entry %u", what, i);
+}
+
+std::vector<RReq> shuffled(std::vector<RReq> rq) {
+    for (size_t k = rq.size(); k > 1; --k) std::swap(rq[k - 1], rq[rnd32() % k]);
+    return rq;
+}
+
+int rangev_main() {
+    const int32_t lens[] = {0, 1, 15, 16, 17, 300, 4097, 70000};
+    // ---- every length, frame and raw, clean and damaged in each way; entries nobody reads and entries
+    //      no one may read; three hints on the same batch ----
+    {
+        std::vector<REntry> es;
+        uint32_t k = 0;
+        for (int32_t l : lens)
+            for (uint8_t kind : {LZ4E_PACK_FRAME, LZ4E_PACK_RAW}) {
+                es.push_back({kind, l, kClean, false});
+                es.push_back({kind, l, l == 0 ? kWrongCrc : (Damage)(kWrongCrc + k++ % 3), false});
+            }
+        const uint32_t named = (uint32_t)es.size();
+        es.push_back({LZ4E_PACK_FRAME, 4097, kClean, true});     // named by nobody
+        es.push_back({LZ4E_PACK_RAW, 300, kWrongCrc, true});     // named by len == 0 requests only
+        es.push_back({2, 300, kClean, true});                    // unknown kinds and negative lengths
+        es.push_back({255, 17, kWrongCrc, true});
+        es.push_back({LZ4E_PACK_RAW, -5, kClean, true});
+        es.push_back({LZ4E_PACK_FRAME, -70000, kWrongCrc, true});
+        // `all`: five ranges of every named entry; `one`: one of the five, a different one from entry to entry
+        std::vector<RReq> all, one;
+        for (uint32_t e = 0; e < named; ++e) {
+            const int32_t l = es[e].len;
+            const RReq five[5] = {{e, 0, l + 1}, {e, l / 2, 4096}, {e, 0, 0}, {e, l, 5}, {e, l > 0 ? l - 1 : 0, 1}};
+            for (const RReq& q : five) all.push_back(q);
+            one.push_back(five[(e / 4) % 2]);
+        }
+        for (std::vector<RReq>* rq : {&all, &one}) {
+            for (uint32_t e = named + 1; e < es.size(); ++e) {
+                rq->push_back({e, 0, 0});
+                rq->push_back({e, 7, 0});
+                if (e > named + 1) rq->push_back({e, 0, 16});
+            }
+            rq->push_back({3, -1, 16});  // invalid requests on a damaged entry, and past the index
+            rq->push_back({3, 1, -16});
+            rq->push_back({(uint32_t)es.size(), 0, 16});
+            rq->push_back({0xFFFFFFFFu, 0, 0});
+        }
+        // (the last hint puts 64 workgroups on every request, so that batch has one request per entry)
+        rangev_case("lengths", es, shuffled(one), false, 70001 + 4096, {1u, 70000u, kHugeHint});
+        rangev_case("ranges", es, shuffled(all), false, 70001 + 4096, {4096u});
+        // the same with a max_end that clamps the long requests
+        rangev_case("clamped", es, shuffled(all), false, 4000, {0u});
+    }
+    // ---- 1, 2, 17 and 300 requests on one entry, interleaved with as many on a damaged one ----
+    for (uint32_t k : {1u, 2u, 17u, 300u}) {
+        const std::vector<REntry> es = {{LZ4E_PACK_FRAME, 4097, kClean, false},
+                                        {LZ4E_PACK_RAW, 300, kFlipLast, false},
+                                        {LZ4E_PACK_RAW, 17, kClean, false},
+                                        {LZ4E_PACK_FRAME, 512, kFlipFirst, false}};
+        std::vector<RReq> rq;
+        for (uint32_t i = 0; i < k; ++i) {
+            rq.push_back({0, (int32_t)(13 * i), (int32_t)(40 + i)});
+            rq.push_back({1, (int32_t)i, i % 3 ? 64 : 0});  // every third of them reads nothing: 0, not BAD_CRC
+            if (i % 5 == 0) rq.push_back({2, (int32_t)(i % 20), 9});
+            if (i % 7 == 0) rq.push_back({3, 0, (int32_t)(1 + i)});
+        }
+        // (two workgroups to a request where the batch is small enough for the emulator)
+        rangev_case("fan-in", es, rq, false, 4200, k <= 17 ? std::vector<uint32_t>{4096u, 64u << 9} : std::vector<uint32_t>{4096u});
+    }
+    // ---- index sizes around a workgroup, null sel and a given one with repeats ----
+    for (uint32_t n : {1u, 255u, 256u, 257u})
+        for (int mode = 0; mode < 3; ++mode) {
+            std::vector<REntry> es;
+            const uint32_t m = mode == 1 && n > 1 ? n - 1 : n;  // mode 1: the last entry is named by nobody
+            for (uint32_t i = 0; i < n; ++i) {
+                const int32_t l = (int32_t)(rnd32() % 41);
+                const uint8_t kind = (i & 1) ? LZ4E_PACK_RAW : LZ4E_PACK_FRAME;
+                if (i >= m || i % 11 == 10) es.push_back({i % 22 == 10 ? (uint8_t)2 : kind, i % 3 ? l : -l - 1, kClean, true});
+                else es.push_back({kind, l, i % 5 == 4 ? (l && (i & 8) ? kFlipFirst : kWrongCrc) : kClean, false});
+            }
+            std::vector<RReq> rq;
+            for (uint32_t j = 0; j < m; ++j) {
+                uint32_t e = mode == 2 ? rnd32() % n : j;
+                const bool readable = !es[e].outside;
+                rq.push_back({e, (int32_t)(rnd32() % 8), readable ? (int32_t)(rnd32() % 48) : 0});
+            }
+            if (n > 1 && mode == 1) es[n - 1] = {LZ4E_PACK_RAW, 33, kWrongCrc, true};
+            rangev_case(mode == 2 ? "index sizes, sel" : "index sizes, null sel", es, rq, mode != 2, 64,
+                        n == 257 && mode == 0 ? std::vector<uint32_t>{1u, 64u << 9} : std::vector<uint32_t>{1u});
+        }
+    // ---- no request at all: nothing is launched ----
+    {
+        const uint64_t before = g_groups_run;
+        rangev_case("no request", {{LZ4E_PACK_RAW, 300, kWrongCrc, true}}, {}, false, 64, {0u, 70000u});
+        rangev_case("no request, no entry", {}, {}, true, 0, {1u});
+        CHECK(g_groups_run == before, "no request: the checksum kernel ran");
+    }
+    if (g_failures) {
+        fprintf(stderr, "emu_crc rangev: %d failures\n", g_failures);
+        return 1;
+    }
+    fprintf(stderr, "emu_crc rangev: %llu workgroups of crc_team_kernel\n", (unsigned long long)g_groups_run);
+    printf("emu_crc rangev ok\n");
+    return 0;
+}
+
 }  // namespace
 
-int main() {
+int main(int argc, char** argv) {
+    if (argc > 1 && strcmp(argv[1], "rangev") == 0) return rangev_main();
     {  // the restatement itself
         const uint8_t nine[] = {'1', '2', '3', '4', '5', '6', '7', '8', '9'};
         uint8_t z[32] = {0};

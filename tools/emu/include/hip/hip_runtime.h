@@ -271,4 +271,8 @@ inline unsigned atomicMin(unsigned* p, unsigned v) {
     while (v < o && !__atomic_compare_exchange_n(p, &o, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
     return o;
 }
+inline unsigned atomicCAS(unsigned* p, unsigned expect, unsigned v) {
+    __atomic_compare_exchange_n(p, &expect, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED);
+    return expect;
+}
 inline bool __syncthreads_or(int v) { return v != 0; }
