@@ -32,6 +32,7 @@
 #include "lz4e_gpu.h"
 #include "lz4e_hostreg.h"
 #include "lz4e_results.h"
+#include "lz4e_store_scratch.h"
 
 static_assert(lz4e::kDecodeAborted == LZ4E_DECODE_ABORTED, "watchdog return value");
 static_assert(lz4e::kCompressAborted == LZ4E_COMPRESS_ABORTED, "compress hand-over return value");
@@ -1064,8 +1065,8 @@ int lz4e_unpack_batch_dev(const uint8_t* packed, const uint64_t* pk_off, const i
 }
 
 // Range read: gather, one partial launch into stream-ordered scratch, team
-// copy.  One allocation: nreq slots of roundup(max_end, 16) bytes, then the
-// partial launch's descriptors (28 bytes per request).
+// copy.  One allocation (lz4e_store_scratch.h, RangeScratch): nreq slots of
+// roundup(max_end, 16) bytes, then the partial launch's descriptors.
 int lz4e_unpack_range_batch_dev(const uint8_t* packed, const uint64_t* pk_off, const int32_t* pk_len,
                                 const uint8_t* pk_kind, uint32_t nentries, const uint32_t* sel,
                                 const int32_t* lo, const int32_t* len, uint8_t* dst, const uint64_t* dst_off,
@@ -1077,18 +1078,18 @@ int lz4e_unpack_range_batch_dev(const uint8_t* packed, const uint64_t* pk_off, c
         return -22;
     }
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint64_t slot = align16((uint64_t)max_end);
-    const uint64_t data = slot * nreq;  // a multiple of 16: the descriptors behind it are aligned
+    const lz4e::RangeScratch L(nreq, max_end);
     uint8_t* scratch = nullptr;
-    if (!hip_ok(hipMallocAsync((void**)&scratch, data + 28ull * nreq + 16, s), "range read scratch")) return -1;
-    uint64_t* g_off = reinterpret_cast<uint64_t*>(scratch + data);
-    uint64_t* s_off = g_off + nreq;
-    int32_t* g_len = reinterpret_cast<int32_t*>(s_off + nreq);
-    int32_t* g_tgt = g_len + nreq;
-    int32_t* g_ret = g_tgt + nreq;
+    if (!hip_ok(hipMallocAsync((void**)&scratch, L.total, s), "range read scratch")) return -1;
+    uint8_t* slots = L.slots.in<uint8_t>(scratch);
+    uint64_t* g_off = L.g_off.in<uint64_t>(scratch);
+    uint64_t* s_off = L.s_off.in<uint64_t>(scratch);
+    int32_t* g_len = L.g_len.in<int32_t>(scratch);
+    int32_t* g_tgt = L.g_tgt.in<int32_t>(scratch);
+    int32_t* g_ret = L.g_ret.in<int32_t>(scratch);
     const lz4e::RangeBatch r{packed, pk_off, pk_len, pk_kind, nentries, sel,   lo,    len,   dst,   dst_off,
-                             ret,    nreq,   max_end, slot,   scratch,  g_off, g_len, g_tgt, s_off, g_ret};
-    lz4e::DecompressBatch d{packed, g_off, g_len, scratch, s_off, g_tgt, g_ret, nreq, max_end};
+                             ret,    nreq,   max_end, L.slot, slots,    g_off, g_len, g_tgt, s_off, g_ret};
+    lz4e::DecompressBatch d{packed, g_off, g_len, slots, s_off, g_tgt, g_ret, nreq, max_end};
     d.partial = true;
     const bool ok = hip_ok(lz4e::launch_range_gather(r, s), "range gather launch") &&
                     hip_ok(lz4e::launch_decompress(d, s), "range decompress launch") &&
@@ -1132,17 +1133,15 @@ int lz4e_unpack_verified_batch_dev(const uint8_t* packed, const uint64_t* pk_off
     if (nblocks == 0) return 0;
     const hipStream_t s = static_cast<hipStream_t>(stream);
     // a stored entry is no longer than the block it decodes to; capacity unknown: a workgroup per entry
-    const uint32_t hint = max_cap ? max_cap : 256 * 64;
-    const uint64_t words = lz4e::crc_partial_words(hint, nblocks);
+    const uint32_t hint = lz4e::crc_hint_or_default(max_cap);
     // one allocation: got[n], masked[n], partial[words], shown[n]
-    uint32_t* scratch = nullptr;
-    if (!hip_ok(hipMallocAsync((void**)&scratch, sizeof(uint32_t) * (2 * (size_t)nblocks + (size_t)words) + nblocks, s),
-                "verified unpack scratch"))
-        return -1;
-    uint32_t* got = scratch;
-    int32_t* masked = reinterpret_cast<int32_t*>(scratch + nblocks);
-    uint32_t* partial = scratch + 2 * (size_t)nblocks;
-    uint8_t* shown = reinterpret_cast<uint8_t*>(partial + words);
+    const lz4e::VerifiedUnpackScratch L(nblocks, lz4e::crc_partial_words(hint, nblocks));
+    uint8_t* scratch = nullptr;
+    if (!hip_ok(hipMallocAsync((void**)&scratch, L.total, s), "verified unpack scratch")) return -1;
+    uint32_t* got = L.got.in<uint32_t>(scratch);
+    int32_t* masked = L.masked.in<int32_t>(scratch);
+    uint32_t* partial = L.partial.in<uint32_t>(scratch);
+    uint8_t* shown = L.shown.in<uint8_t>(scratch);
     const lz4e::CrcBatch c{packed, pk_off, packed, pk_off, pk_kind, pk_len, got, nblocks, hint};
     lz4e::DecompressBatch d{packed, pk_off, masked, dst, dst_off, dst_cap, ret, nblocks, max_cap};
     lz4e::UnpackRawBatch r{packed, pk_off, pk_len, shown, dst, dst_off, dst_cap, ret, nblocks, max_cap};
@@ -1159,9 +1158,10 @@ int lz4e_unpack_verified_batch_dev(const uint8_t* packed, const uint64_t* pk_off
 
 // The verified range read: lz4e_unpack_range_batch_dev's three steps, on the
 // shadow kind column `shown`, between the election and checksum in front and
-// the ret kernel behind (lz4e_gpu.h, RangeVerifyBatch).  One allocation: the
-// range read's slots and descriptors, then c_off[nreq] (8-byte words first),
-// c_len[nreq], got[nreq], owner[nentries], partial[words], shown[nentries].
+// the ret kernel behind (lz4e_gpu.h, RangeVerifyBatch).  One allocation
+// (lz4e_store_scratch.h, RangeScratch): the range read's slots and
+// descriptors and c_off[nreq], c_len[nreq], got[nreq], owner[nentries],
+// partial[words], shown[nentries].
 int lz4e_unpack_range_verified_batch_dev(const uint8_t* packed, const uint64_t* pk_off, const int32_t* pk_len,
                                          const uint8_t* pk_kind, const uint32_t* pk_crc, uint32_t nentries,
                                          const uint32_t* sel, const int32_t* lo, const int32_t* len, uint8_t* dst,
@@ -1174,31 +1174,28 @@ int lz4e_unpack_range_verified_batch_dev(const uint8_t* packed, const uint64_t* 
         return -22;
     }
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint32_t hint = max_len ? max_len : 256 * 64;  // unknown: a workgroup per entry
-    const uint64_t words = lz4e::crc_partial_words(hint, nreq);
-    const uint64_t slot = align16((uint64_t)max_end);
-    const uint64_t data = slot * nreq;  // a multiple of 16: the words behind it are aligned
+    const uint32_t hint = lz4e::crc_hint_or_default(max_len);
+    const lz4e::RangeScratch L(nreq, max_end, true, nentries, lz4e::crc_partial_words(hint, nreq));
     uint8_t* scratch = nullptr;
-    if (!hip_ok(hipMallocAsync((void**)&scratch, data + 44ull * nreq + 5ull * nentries + 4 * words + 16, s),
-                "verified range read scratch"))
-        return -1;
-    uint64_t* g_off = reinterpret_cast<uint64_t*>(scratch + data);
-    uint64_t* s_off = g_off + nreq;
-    uint64_t* c_off = s_off + nreq;
-    int32_t* g_len = reinterpret_cast<int32_t*>(c_off + nreq);
-    int32_t* g_tgt = g_len + nreq;
-    int32_t* g_ret = g_tgt + nreq;
-    int32_t* c_len = g_ret + nreq;
-    uint32_t* got = reinterpret_cast<uint32_t*>(c_len + nreq);
-    uint32_t* owner = got + nreq;
-    uint32_t* partial = owner + nentries;
-    uint8_t* shown = reinterpret_cast<uint8_t*>(partial + words);
+    if (!hip_ok(hipMallocAsync((void**)&scratch, L.total, s), "verified range read scratch")) return -1;
+    uint8_t* slots = L.slots.in<uint8_t>(scratch);
+    uint64_t* g_off = L.g_off.in<uint64_t>(scratch);
+    uint64_t* s_off = L.s_off.in<uint64_t>(scratch);
+    uint64_t* c_off = L.c_off.in<uint64_t>(scratch);
+    int32_t* g_len = L.g_len.in<int32_t>(scratch);
+    int32_t* g_tgt = L.g_tgt.in<int32_t>(scratch);
+    int32_t* g_ret = L.g_ret.in<int32_t>(scratch);
+    int32_t* c_len = L.c_len.in<int32_t>(scratch);
+    uint32_t* got = L.got.in<uint32_t>(scratch);
+    uint32_t* owner = L.owner.in<uint32_t>(scratch);
+    uint32_t* partial = L.partial.in<uint32_t>(scratch);
+    uint8_t* shown = L.shown.in<uint8_t>(scratch);
     const lz4e::RangeVerifyBatch v{pk_off, pk_len, pk_kind, pk_crc, nentries, sel,   lo,    len,
                                    ret,    nreq,   owner,   shown,  c_off,    c_len, got};
     const lz4e::CrcBatch c{packed, c_off, nullptr, nullptr, nullptr, c_len, got, nreq, hint};
-    const lz4e::RangeBatch r{packed, pk_off, pk_len, shown, nentries, sel,   lo,    len,   dst,   dst_off,
-                             ret,    nreq,   max_end, slot,  scratch,  g_off, g_len, g_tgt, s_off, g_ret};
-    lz4e::DecompressBatch d{packed, g_off, g_len, scratch, s_off, g_tgt, g_ret, nreq, max_end};
+    const lz4e::RangeBatch r{packed, pk_off, pk_len, shown,  nentries, sel,   lo,    len,   dst,   dst_off,
+                             ret,    nreq,   max_end, L.slot, slots,    g_off, g_len, g_tgt, s_off, g_ret};
+    lz4e::DecompressBatch d{packed, g_off, g_len, slots, s_off, g_tgt, g_ret, nreq, max_end};
     d.partial = true;
     const bool ok = hip_ok(lz4e::launch_range_verify_init(v, s), "verified range init launch") &&
                     hip_ok(lz4e::launch_range_verify_elect(v, s), "verified range elect launch") &&

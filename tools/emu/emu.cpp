@@ -1,13 +1,11 @@
 // Lane emulator of the LZ4E compress kernel (debug/test tooling, tools/emu):
 // compiles the unmodified kernel source (and csrc/lz4e_wave.h, with
-// -DLZ4E_EMU) as host C++ and runs each workgroup as 64 threads per wave.
+// -DLZ4E_EMU) as host C++ and runs each workgroup as 64 threads per wave
+// (emu_harness.h: kEmuThreads).
 #include <stdint.h>
 #include <string.h>
-#include <memory>
-#include <thread>
-#include <vector>
 
-#include <hip/hip_runtime.h>
+#include "emu_harness.h"
 
 namespace lz4e {
 namespace {
@@ -29,32 +27,11 @@ namespace lz4e {
 int launch_order_mode(bool) { return kOrderNever; }
 }  // namespace lz4e
 
-thread_local EmuWave* g_emu_wave;
-thread_local uint32_t g_emu_lane;
-thread_local EmuBarrier* g_emu_group;
-dim3 blockIdx, gridDim;
-thread_local dim3 threadIdx;
-
-void emu_launch(uint32_t nblocks, uint32_t threads, std::function<void()> body) {
-    const uint32_t nw = (threads + 63) / 64;
-    gridDim = dim3(nblocks);
-    for (uint32_t b = 0; b < nblocks; ++b) {
-        blockIdx = dim3(b);
-        std::unique_ptr<EmuWave[]> waves(new EmuWave[nw]);
-        EmuBarrier group((std::ptrdiff_t)(64 * nw));
-        memset(lz4e::smem, 0xA5, sizeof(lz4e::smem));  // LDS is not zeroed on the GPU
-        std::vector<std::thread> th;
-        for (uint32_t t = 0; t < 64 * nw; ++t)
-            th.emplace_back([&, t]() {
-                g_emu_wave = &waves[t / 64];
-                g_emu_lane = t % 64;
-                g_emu_group = &group;
-                threadIdx = dim3(t);
-                body();
-            });
-        for (auto& x : th) x.join();
-    }
-}
+// Every kernel of this build (the decoders of emu_dec.cpp included) runs as
+// fresh host threads, 64 per wave; before each workgroup the emulated LDS is
+// filled, since LDS is not zeroed on the GPU.
+const EmuKernelMode emu_modes[] = {{nullptr, kEmuThreads}};
+static const bool g_lds_hook = (emu_block_hook = [] { memset(lz4e::smem, 0xA5, sizeof(lz4e::smem)); }, true);
 
 extern "C" int emu_compress_batch(const uint8_t* src, const uint64_t* src_off, const uint32_t* src_len,
                                   const uint8_t* table_type, uint8_t* dst, const uint64_t* dst_off,

@@ -14,134 +14,32 @@
 //
 // The kernels read the CALLER's memory at byte granularity.  So every entry
 // here is its own heap allocation that ends exactly at its last byte (ASan's
-// redzone follows it), placed at a chosen alignment mod 16 as in emu_pack.cpp.
+// redzone follows it), placed at a chosen alignment mod 16 (emu_harness.h, Buf).
 // An entry that must not be read is an allocation of 0 bytes or an offset
 // outside every allocation.  Expected values come from ref_crc below, a
 // bitwise restatement of CRC-32C that shares nothing with the kernel's tables.
 //
 // crc_team_kernel fills a table in LDS behind a barrier and XORs across
-// lanes, so a workgroup of it is 256 host threads (4 emulated waves) that
-// live as long as the program; workgroups run one after the other.  The
-// other kernels have neither, so their lanes run one after the other on the
-// calling thread.
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
+// lanes, so it runs on the harness's pool of lane threads; the other kernels
+// have neither, so their lanes run one after the other on the calling thread,
+// and the pack scan kernels are not run here: the table next to main.
 #include <algorithm>
-#include <memory>
-#include <thread>
-#include <vector>
 
-#include <hip/hip_runtime.h>
+#include "emu_harness.h"
 #undef __shared__
 #define __shared__ static
-void emu_launch_named(const char* kernel, uint32_t nblocks, uint32_t threads, std::function<void()> body);
-#undef hipLaunchKernelGGL
-#define hipLaunchKernelGGL(k, grid, block, lds, stream, ...) \
-    emu_launch_named(#k, (grid).x, (block).x, [&]() { k(__VA_ARGS__); })
 
 #include "lz4e_crc.hip"
 #include "lz4e_pack.hip"
 
 #include "lz4e.h"
-
-#if defined(__has_feature)
-#if __has_feature(address_sanitizer)
-#include <sanitizer/asan_interface.h>
-#define EMU_POISON(p, n) __asan_poison_memory_region((p), (n))
-#define EMU_UNPOISON(p, n) __asan_unpoison_memory_region((p), (n))
-#endif
-#endif
-#ifndef EMU_POISON
-#define EMU_POISON(p, n) ((void)0)
-#define EMU_UNPOISON(p, n) ((void)0)
-#endif
-
-thread_local EmuWave* g_emu_wave;
-thread_local uint32_t g_emu_lane;
-thread_local EmuBarrier* g_emu_group;
-dim3 blockIdx, gridDim;
-thread_local dim3 threadIdx;
-
-namespace {
-constexpr uint32_t kLanes = 256;
-struct LanePool {
-    EmuBarrier start{kLanes + 1}, end{kLanes + 1}, group{kLanes};
-    EmuWave waves[kLanes / 64];
-    std::function<void()>* body = nullptr;
-    bool quit = false;
-    std::vector<std::thread> th;
-    LanePool() {
-        for (uint32_t t = 0; t < kLanes; ++t)
-            th.emplace_back([this, t]() {
-                g_emu_wave = &waves[t / 64];
-                g_emu_lane = t % 64;
-                g_emu_group = &group;
-                threadIdx = dim3(t);
-                for (;;) {
-                    start.arrive_and_wait();
-                    if (quit) return;
-                    (*body)();
-                    end.arrive_and_wait();
-                }
-            });
-    }
-    ~LanePool() {
-        quit = true;
-        start.arrive_and_wait();
-        for (auto& x : th) x.join();
-    }
-};
-uint64_t g_groups_run = 0;
-}  // namespace
-
-void emu_launch(uint32_t nblocks, uint32_t threads, std::function<void()> body) {
-    static LanePool pool;
-    if (threads != kLanes) abort();
-    gridDim = dim3(nblocks);
-    pool.body = &body;
-    for (uint32_t b = 0; b < nblocks; ++b) {
-        blockIdx = dim3(b);
-        pool.start.arrive_and_wait();
-        pool.end.arrive_and_wait();
-    }
-    g_groups_run += nblocks;
-}
-
-void emu_launch_named(const char* kernel, uint32_t nblocks, uint32_t threads, std::function<void()> body) {
-    if (strstr(kernel, "crc_team")) return emu_launch(nblocks, threads, body);
-    if (strstr(kernel, "pack_tile") || strstr(kernel, "pack_index")) abort();  // not run here
-    gridDim = dim3(nblocks);
-    for (uint32_t b = 0; b < nblocks; ++b) {
-        blockIdx = dim3(b);
-        for (uint32_t t = 0; t < threads; ++t) {
-            threadIdx = dim3(t);
-            g_emu_lane = t % 64;
-            body();
-        }
-    }
-}
-
-namespace {
-
-int g_failures = 0;
-#define CHECK(c, ...)                        \
-    do {                                     \
-        if (!(c)) {                          \
-            fprintf(stderr, "FAIL: " __VA_ARGS__); \
-            fprintf(stderr, "\n");           \
-            g_failures++;                    \
-        }                                    \
-    } while (0)
+#include "lz4e_store_scratch.h"
 
 uint32_t g_rng = 2463534242u;
-uint32_t rnd32() {
-    g_rng = g_rng * 1664525u + 1013904223u;
-    return g_rng >> 8;
-}
+uint32_t rnd32() { return emu_lcg(g_rng) >> 8; }
 uint8_t rnd() { return (uint8_t)rnd32(); }
+
+namespace {
 
 // CRC-32C bit by bit.
 uint32_t ref_crc(const uint8_t* p, size_t n) {
@@ -153,53 +51,51 @@ uint32_t ref_crc(const uint8_t* p, size_t n) {
     return c ^ 0xFFFFFFFFu;
 }
 
-constexpr uint8_t kCanary = 0xC3, kFill = 0x5A;
 constexpr uint32_t kHugeHint = 0x7E000000u;
 
-// n bytes at alignment `align` (mod 16), ending where their heap block ends.
-struct Buf {
-    uint8_t* base;
-    uint8_t* p;
-    size_t align, n;
-    Buf(size_t align_, size_t n_) : align(align_ & 15), n(n_) {
-        base = static_cast<uint8_t*>(malloc(align + n));
-        if (!base) abort();
-        p = base + align;
-        memset(base, kCanary, align);
-        EMU_POISON(base, align & ~size_t(7));
-    }
-    Buf(const Buf&) = delete;
-    Buf& operator=(const Buf&) = delete;
-    ~Buf() {
-        EMU_UNPOISON(base, align & ~size_t(7));
-        free(base);
-    }
-    void fill_random() {
-        for (size_t i = 0; i < n; ++i) p[i] = rnd();
-    }
-    void fill(uint8_t v) { memset(p, v, n); }
-    bool all(uint8_t v) const {
-        for (size_t i = 0; i < n; ++i)
-            if (p[i] != v) return false;
-        return true;
-    }
-    bool canary_ok() const {
-        for (size_t i = align & ~size_t(7); i < align; ++i)
-            if (base[i] != kCanary) return false;
-        return true;
-    }
-    template <class T>
-    T* as() {
-        return reinterpret_cast<T*>(p);
-    }
+// The carving lz4e_host.hip does (csrc/lz4e_store_scratch.h) on its own: every
+// array holds its elements, lies inside [0, total) at a multiple of its
+// element size and overlaps no other; `total` has not wrapped.
+struct LArray {
+    const char* name;
+    lz4e::ScratchArray a;
+    size_t elem;
+    uint64_t count;
 };
-typedef std::unique_ptr<Buf> BufP;
-
-const uint8_t* lowest(const std::vector<BufP>& v) {
-    const uint8_t* lo = nullptr;
-    for (const BufP& b : v)
-        if (!lo || b->p < lo) lo = b->p;
-    return lo;
+void layout_check(const char* what, const std::vector<LArray>& as, size_t total) {
+    unsigned __int128 need = 0;
+    for (size_t i = 0; i < as.size(); ++i) {
+        const lz4e::ScratchArray& a = as[i].a;
+        need += (unsigned __int128)as[i].elem * as[i].count;
+        CHECK(a.bytes == (unsigned __int128)as[i].elem * as[i].count, "%s: %s holds %zu bytes", what, as[i].name, a.bytes);
+        CHECK(a.offset + a.bytes >= a.offset && a.offset + a.bytes <= total, "%s: %s ends outside the allocation", what, as[i].name);
+        CHECK(a.offset % as[i].elem == 0, "%s: %s at offset %zu", what, as[i].name, a.offset);
+        for (size_t k = 0; k < i; ++k)
+            CHECK(a.offset >= as[k].a.offset + as[k].a.bytes || as[k].a.offset >= a.offset + a.bytes || !a.bytes || !as[k].a.bytes,
+                  "%s: %s overlaps %s", what, as[i].name, as[k].name);
+    }
+    CHECK(total >= need, "%s: a total of %zu bytes", what, total);
+}
+void layout_sweep() {
+    for (uint32_t n : {0u, 1u, 2u, 3u, 255u, 256u, 257u})
+        for (uint64_t words : {(uint64_t)0, (uint64_t)1, (uint64_t)5, (uint64_t)64 * n}) {
+            const lz4e::VerifiedUnpackScratch U(n, words);
+            layout_check("verified unpack", {{"got", U.got, 4, n}, {"masked", U.masked, 4, n}, {"partial", U.partial, 4, words}, {"shown", U.shown, 1, n}},
+                         U.total);
+            for (uint32_t ne : {0u, 1u, 7u, 300u})
+                for (uint32_t max_end : {0u, 1u, 15u, 16u, 17u, 4097u, 0x7FFFFFF0u})
+                    for (uint64_t v : {0u, 1u}) {
+                        const lz4e::RangeScratch L(n, max_end, v != 0, ne, words);
+                        const size_t slot = ((size_t)max_end + 15) / 16 * 16;
+                        CHECK(L.slot == slot, "range read: a slot of %zu bytes for max_end %u", L.slot, max_end);
+                        layout_check(v ? "verified range read" : "range read",
+                                     {{"slots", L.slots, 16, (uint64_t)n * (slot / 16)}, {"g_off", L.g_off, 8, n}, {"s_off", L.s_off, 8, n},
+                                      {"c_off", L.c_off, 8, v * n}, {"g_len", L.g_len, 4, n}, {"g_tgt", L.g_tgt, 4, n}, {"g_ret", L.g_ret, 4, n},
+                                      {"c_len", L.c_len, 4, v * n}, {"got", L.got, 4, v * n}, {"owner", L.owner, 4, v * ne},
+                                      {"partial", L.partial, 4, v * words}, {"shown", L.shown, 1, v * ne}},
+                                     L.total);
+                    }
+        }
 }
 
 // launch_crc with the scratch lz4e_host.hip would take from the pool: an
@@ -326,9 +222,10 @@ constexpr int32_t kDecoded = 424242;  // the stand-in decoder's ret for an entry
 // entries (align 1): checksum, mask, stand-in decoders, raw copy, ret.
 void verify_case(const char* what, const std::vector<VEntry>& es, uint32_t packed_align, uint32_t hint) {
     const uint32_t n = (uint32_t)es.size();
+    const lz4e::VerifiedUnpackScratch L(n, lz4e::crc_partial_words(hint, n));  // (partial: run_crc's)
     Buf pk_off(0, 8 * ((size_t)n + 1)), pk_len(0, 4 * (size_t)n), pk_kind(0, n), pk_crc(0, 4 * (size_t)n),
-        dst_off(0, 8 * (size_t)n), dst_cap(0, 4 * (size_t)n), ret(0, 4 * (size_t)n), masked(0, 4 * (size_t)n),
-        got(0, 4 * (size_t)n), shown(0, n);
+        dst_off(0, 8 * (size_t)n), dst_cap(0, 4 * (size_t)n), ret(0, 4 * (size_t)n), masked(0, L.masked.bytes),
+        got(0, L.got.bytes), shown(0, L.shown.bytes);
     uint64_t at = 0;
     for (uint32_t i = 0; i < n; ++i) {
         pk_off.as<uint64_t>()[i] = es[i].outside ? ((uint64_t)1 << 46) + i : at;
@@ -413,8 +310,8 @@ struct RReq {
 
 // lz4e_unpack_range_verified_batch_dev's composition, launch for launch as
 // lz4e_host.hip issues it, once per hint.  Every entry is an allocation of its
-// own (exactly pk_len bytes), every scratch array one of exactly the size the
-// header states, every destination one of exactly the bytes its request must
+// own (exactly pk_len bytes), every scratch array one of exactly the size
+// lz4e_store_scratch.h states, every destination one of exactly the bytes its request must
 // get.  The decoders' part is played by a stand-in that takes a frame's bytes
 // for its data: -1 for a length of 0 before it reads or writes anything, else
 // the first min(length, target) bytes into the request's slot.  Expected
@@ -477,7 +374,7 @@ void rangev_case(const char* what, const std::vector<REntry>& es, const std::vec
     }
     uint32_t nwanted = 0;
     for (uint32_t i = 0; i < n; ++i) nwanted += wanted[i];
-    const uint64_t slot = ((uint64_t)max_end + 15) & ~(uint64_t)15;
+    const uint64_t slot = lz4e::RangeScratch(m, max_end).slot;
     for (uint32_t hint : hints) {
         std::vector<BufP> dsts;
         for (uint32_t j = 0; j < m; ++j) {
@@ -490,9 +387,10 @@ void rangev_case(const char* what, const std::vector<REntry>& es, const std::vec
         Buf dst_off(0, 8 * (size_t)m), ret(0, 4 * (size_t)m);
         for (uint32_t j = 0; j < m; ++j) dst_off.as<uint64_t>()[j] = (uint64_t)(dsts[j]->p - dst);
         const uint64_t words = lz4e::crc_partial_words(hint, m);
-        Buf slots(0, (size_t)(slot * m)), g_off(0, 8 * (size_t)m), s_off(0, 8 * (size_t)m), c_off(0, 8 * (size_t)m),
-            g_len(0, 4 * (size_t)m), g_tgt(0, 4 * (size_t)m), g_ret(0, 4 * (size_t)m), c_len(0, 4 * (size_t)m),
-            got(0, 4 * (size_t)m), owner(0, 4 * (size_t)n), partial(0, 4 * (size_t)words), shown(0, n);
+        const lz4e::RangeScratch L(m, max_end, true, n, words);
+        Buf slots(0, L.slots.bytes), g_off(0, L.g_off.bytes), s_off(0, L.s_off.bytes), c_off(0, L.c_off.bytes),
+            g_len(0, L.g_len.bytes), g_tgt(0, L.g_tgt.bytes), g_ret(0, L.g_ret.bytes), c_len(0, L.c_len.bytes),
+            got(0, L.got.bytes), owner(0, L.owner.bytes), partial(0, L.partial.bytes), shown(0, L.shown.bytes);
         for (Buf* b : {&ret, &slots, &g_off, &s_off, &c_off, &g_len, &g_tgt, &g_ret, &c_len, &got, &owner, &partial, &shown})
             b->fill(kFill);
         const uint32_t* selp = null_sel ? nullptr : sel.as<uint32_t>();
@@ -554,6 +452,7 @@ std::vector<RReq> shuffled(std::vector<RReq> rq) {
 }
 
 int rangev_main() {
+    layout_sweep();
     const int32_t lens[] = {0, 1, 15, 16, 17, 300, 4097, 70000};
     // ---- every length, frame and raw, clean and damaged in each way; entries nobody reads and entries
     //      no one may read; three hints on the same batch ----
@@ -641,19 +540,24 @@ int rangev_main() {
         rangev_case("no request, no entry", {}, {}, true, 0, {1u});
         CHECK(g_groups_run == before, "no request: the checksum kernel ran");
     }
-    if (g_failures) {
-        fprintf(stderr, "emu_crc rangev: %d failures\n", g_failures);
-        return 1;
-    }
     fprintf(stderr, "emu_crc rangev: %llu workgroups of crc_team_kernel\n", (unsigned long long)g_groups_run);
-    printf("emu_crc rangev ok\n");
-    return 0;
+    return emu_finish("emu_crc rangev");
 }
 
 }  // namespace
 
+// No default: lz4e_pack.hip's other kernels (the pack scan among them) are not run here.
+const EmuKernelMode emu_modes[] = {
+    {"crc_team_kernel", kEmuPool},                {"crc_combine_kernel", kEmuSerial},
+    {"unpack_verify_mask_kernel", kEmuSerial},    {"unpack_verify_ret_kernel", kEmuSerial},
+    {"range_verify_init_kernel", kEmuSerial},     {"range_verify_elect_kernel", kEmuSerial},
+    {"range_verify_verdict_kernel", kEmuSerial},  {"range_verify_ret_kernel", kEmuSerial},
+    {"unpack_raw_kernel", kEmuSerial},            {"range_gather_kernel", kEmuSerial},
+    {"range_deliver_kernel", kEmuSerial},         {nullptr, kEmuNone}};
+
 int main(int argc, char** argv) {
     if (argc > 1 && strcmp(argv[1], "rangev") == 0) return rangev_main();
+    layout_sweep();
     {  // the restatement itself
         const uint8_t nine[] = {'1', '2', '3', '4', '5', '6', '7', '8', '9'};
         uint8_t z[32] = {0};
@@ -729,11 +633,6 @@ int main(int argc, char** argv) {
         verify_case("verify", es, hint == 4096u ? 0 : 11, hint);
     }
     verify_case("verify, no entry", {}, 0, 4096);
-    if (g_failures) {
-        fprintf(stderr, "emu_crc: %d failures\n", g_failures);
-        return 1;
-    }
     fprintf(stderr, "emu_crc: %llu workgroups of crc_team_kernel\n", (unsigned long long)g_groups_run);
-    printf("emu_crc ok\n");
-    return 0;
+    return emu_finish("emu_crc");
 }

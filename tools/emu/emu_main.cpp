@@ -41,17 +41,7 @@
 #include <string>
 #include <vector>
 
-#if defined(__has_feature)
-#if __has_feature(address_sanitizer)
-#include <sanitizer/asan_interface.h>
-#define EMU_POISON(p, n) ASAN_POISON_MEMORY_REGION(p, n)
-#define EMU_UNPOISON(p, n) ASAN_UNPOISON_MEMORY_REGION(p, n)
-#endif
-#endif
-#ifndef EMU_POISON
-#define EMU_POISON(p, n) ((void)0)
-#define EMU_UNPOISON(p, n) ((void)0)
-#endif
+#include "emu_harness.h"  // EMU_POISON, EMU_UNPOISON
 
 static unsigned g_src_skew = 0, g_dst_skew = 0;
 static bool g_skewed = false;  // without --skew the buffers start at the heap block's start

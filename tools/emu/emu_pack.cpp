@@ -1,7 +1,7 @@
 // Lane emulator of the packed frame store's kernels (debug/test tooling,
 // tools/emu): compiles the unmodified csrc/lz4e_pack.hip as host C++ and runs
-// the four pack kernels, unpack_mask_kernel and unpack_raw_kernel with every
-// lane a host thread, under the same emulated <hip/hip_runtime.h> as the other
+// the four pack kernels, unpack_mask_kernel and unpack_raw_kernel lane by
+// lane, under the same emulated <hip/hip_runtime.h> as the other
 // kernel files (the decoders that run between the two unpack kernels are
 // emu_main's business).  Stand-alone (its own main): built by
 // EMU_PACK=1 build.sh, run by tests/test_emulator_pack.py under ASan + UBSan.
@@ -14,194 +14,29 @@
 // frame slot, every source block, `packed`, every unpack destination and
 // every index array here is its own heap allocation that ends exactly at the
 // last byte the contract allows (ASan's redzone follows it), placed at a
-// chosen alignment mod 16 as in emu_sg.cpp: the whole 8-byte granules of the
-// prefix are poisoned, the up to 7 bytes left hold a canary.  A frame entry's
-// source and a raw entry's frame slot are allocations of 0 bytes: reading
-// them at all is a report.
+// chosen alignment mod 16 with a poisoned prefix and a canary (emu_harness.h,
+// Buf).  A frame entry's source and a raw entry's frame slot are allocations
+// of 0 bytes: reading them at all is a report.
 //
-// The scan kernels use cross-lane operations and workgroup barriers, so a
-// workgroup of theirs is 256 host threads (4 emulated waves) that live as
-// long as the program (the one-wave scan of the tile sums: 64 threads of its
-// own); workgroups run one after the other.  The copy, mask
-// and raw-copy kernels have neither, so their lanes run one after the other
-// on the calling thread (the launch macro below hands the kernel's name on).
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <memory>
-#include <thread>
-#include <vector>
-
-#include <hip/hip_runtime.h>
+// The scan kernels use cross-lane operations and workgroup barriers, so they
+// run on the harness's pool of lane threads (the one-wave scan of the tile
+// sums on 64 of them); the copy, mask and raw-copy kernels and the range
+// read's two have neither, so their lanes run one after the other on the
+// calling thread: the table next to main.
+#include "emu_harness.h"
 #undef __shared__
 #define __shared__ static
-void emu_launch_named(const char* kernel, uint32_t nblocks, uint32_t threads, std::function<void()> body);
-#undef hipLaunchKernelGGL
-#define hipLaunchKernelGGL(k, grid, block, lds, stream, ...) \
-    emu_launch_named(#k, (grid).x, (block).x, [&]() { k(__VA_ARGS__); })
 
 #include "lz4e_pack.hip"
 
 #include "lz4e.h"
-
-#if defined(__has_feature)
-#if __has_feature(address_sanitizer)
-#include <sanitizer/asan_interface.h>
-#define EMU_POISON(p, n) __asan_poison_memory_region((p), (n))
-#define EMU_UNPOISON(p, n) __asan_unpoison_memory_region((p), (n))
-#endif
-#endif
-#ifndef EMU_POISON
-#define EMU_POISON(p, n) ((void)0)
-#define EMU_UNPOISON(p, n) ((void)0)
-#endif
-
-thread_local EmuWave* g_emu_wave;
-thread_local uint32_t g_emu_lane;
-thread_local EmuBarrier* g_emu_group;
-dim3 blockIdx, gridDim;
-thread_local dim3 threadIdx;
-
-namespace {
-constexpr uint32_t kLanes = 256;  // the tile kernels' workgroup
-struct LanePool {
-    EmuBarrier start{kLanes + 1}, end{kLanes + 1}, group{kLanes};
-    EmuWave waves[kLanes / 64];
-    std::function<void()>* body = nullptr;
-    bool quit = false;
-    std::vector<std::thread> th;
-    LanePool() {
-        for (uint32_t t = 0; t < kLanes; ++t)
-            th.emplace_back([this, t]() {
-                g_emu_wave = &waves[t / 64];
-                g_emu_lane = t % 64;
-                g_emu_group = &group;
-                threadIdx = dim3(t);
-                for (;;) {
-                    start.arrive_and_wait();
-                    if (quit) return;
-                    (*body)();
-                    end.arrive_and_wait();
-                }
-            });
-    }
-    ~LanePool() {
-        quit = true;
-        start.arrive_and_wait();
-        for (auto& x : th) x.join();
-    }
-};
-}  // namespace
-
-void emu_launch(uint32_t nblocks, uint32_t threads, std::function<void()> body) {
-    gridDim = dim3(nblocks);
-    if (threads == 64 && nblocks == 1) {  // pack_tile_scan_kernel
-        EmuWave wave;
-        blockIdx = dim3(0);
-        std::vector<std::thread> th;
-        for (uint32_t t = 0; t < 64; ++t)
-            th.emplace_back([&, t]() {
-                g_emu_wave = &wave;
-                g_emu_lane = t;
-                threadIdx = dim3(t);
-                body();
-            });
-        for (auto& x : th) x.join();
-        return;
-    }
-    static LanePool pool;
-    if (threads != kLanes) abort();
-    pool.body = &body;
-    for (uint32_t b = 0; b < nblocks; ++b) {
-        blockIdx = dim3(b);
-        pool.start.arrive_and_wait();
-        pool.end.arrive_and_wait();
-    }
-}
-
-void emu_launch_named(const char* kernel, uint32_t nblocks, uint32_t threads, std::function<void()> body) {
-    if (strstr(kernel, "pack_tile") || strstr(kernel, "pack_index")) return emu_launch(nblocks, threads, body);
-    gridDim = dim3(nblocks);
-    for (uint32_t b = 0; b < nblocks; ++b) {
-        blockIdx = dim3(b);
-        for (uint32_t t = 0; t < threads; ++t) {
-            threadIdx = dim3(t);
-            g_emu_lane = t % 64;
-            body();
-        }
-    }
-}
-
-namespace {
-
-int g_failures = 0;
-#define CHECK(c, ...)                        \
-    do {                                     \
-        if (!(c)) {                          \
-            fprintf(stderr, "FAIL: " __VA_ARGS__); \
-            fprintf(stderr, "\n");           \
-            g_failures++;                    \
-        }                                    \
-    } while (0)
+#include "lz4e_store_scratch.h"
 
 uint32_t g_rng = 2463534242u;
-uint32_t rnd32() {
-    g_rng = g_rng * 1664525u + 1013904223u;
-    return g_rng >> 8;
-}
+uint32_t rnd32() { return emu_lcg(g_rng) >> 8; }
 uint8_t rnd() { return (uint8_t)rnd32(); }
 
-constexpr uint8_t kCanary = 0xC3, kFill = 0x5A;
-
-// n bytes at alignment `align` (mod 16), ending where their heap block ends.
-struct Buf {
-    uint8_t* base;
-    uint8_t* p;
-    size_t align, n;
-    Buf(size_t align_, size_t n_) : align(align_ & 15), n(n_) {
-        base = static_cast<uint8_t*>(malloc(align + n));
-        if (!base) abort();
-        p = base + align;
-        memset(base, kCanary, align);
-        EMU_POISON(base, align & ~size_t(7));
-    }
-    Buf(const Buf&) = delete;
-    Buf& operator=(const Buf&) = delete;
-    ~Buf() {
-        EMU_UNPOISON(base, align & ~size_t(7));
-        free(base);
-    }
-    void fill_random() {
-        for (size_t i = 0; i < n; ++i) p[i] = rnd();
-    }
-    void fill(uint8_t v) { memset(p, v, n); }
-    bool all(uint8_t v) const {
-        for (size_t i = 0; i < n; ++i)
-            if (p[i] != v) return false;
-        return true;
-    }
-    bool canary_ok() const {
-        for (size_t i = align & ~size_t(7); i < align; ++i)
-            if (base[i] != kCanary) return false;
-        return true;
-    }
-    template <class T>
-    T* as() {
-        return reinterpret_cast<T*>(p);
-    }
-};
-typedef std::unique_ptr<Buf> BufP;
-
-// The lowest address of a set of buffers: the batch's base pointer, so that
-// every offset is a forward one.
-const uint8_t* lowest(const std::vector<BufP>& v) {
-    const uint8_t* lo = nullptr;
-    for (const BufP& b : v)
-        if (!lo || b->p < lo) lo = b->p;
-    return lo;
-}
+namespace {
 
 struct Entry {
     uint32_t src_len;
@@ -380,10 +215,11 @@ void range_case(const char* what, const std::vector<UEntry>& es, const std::vect
     uint32_t max_end = 0;
     for (const RReq& q : rq)
         if (q.lo >= 0 && q.len >= 0 && (uint32_t)q.lo + (uint32_t)q.len > max_end) max_end = (uint32_t)q.lo + (uint32_t)q.len;
-    const uint64_t slot = ((uint64_t)max_end + 15) & ~15ull;
+    const lz4e::RangeScratch L(m, max_end);  // lz4e_unpack_range_batch_dev's arrays, an allocation each
+    const uint64_t slot = L.slot;
     Buf sel(0, 4 * (size_t)m), lo(0, 4 * (size_t)m), len(0, 4 * (size_t)m), dst_off(0, 8 * (size_t)m), ret(0, 4 * (size_t)m);
-    Buf g_off(0, 8 * (size_t)m), s_off(0, 8 * (size_t)m), g_len(0, 4 * (size_t)m), g_tgt(0, 4 * (size_t)m),
-        g_ret(0, 4 * (size_t)m), scratch(0, slot * m);
+    Buf g_off(0, L.g_off.bytes), s_off(0, L.s_off.bytes), g_len(0, L.g_len.bytes), g_tgt(0, L.g_tgt.bytes),
+        g_ret(0, L.g_ret.bytes), scratch(0, L.slots.bytes);
     scratch.fill_random();
     // ---- the restatement ----
     std::vector<int32_t> want(m);
@@ -486,12 +322,7 @@ int range_main() {
         range_case("null sel", es, id, false, pa);
     }
     range_case("no request", es, {}, true, 0);
-    if (g_failures) {
-        fprintf(stderr, "emu_pack range: %d failures\n", g_failures);
-        return 1;
-    }
-    printf("emu_pack range ok\n");
-    return 0;
+    return emu_finish("emu_pack range");
 }
 
 const uint32_t kLens[] = {0, 1, 15, 16, 17, 31, 33, 511, 512, 4096, 4097, 70000};
@@ -502,6 +333,12 @@ Entry entry_of(uint32_t len, bool frame, uint32_t sa, uint32_t fa) {
 }
 
 }  // namespace
+
+const EmuKernelMode emu_modes[] = {{"pack_tile_sum_kernel", kEmuPool},   {"pack_tile_scan_kernel", kEmuPool},
+                                   {"pack_index_kernel", kEmuPool},      {"pack_copy_kernel", kEmuSerial},
+                                   {"unpack_mask_kernel", kEmuSerial},   {"unpack_raw_kernel", kEmuSerial},
+                                   {"range_gather_kernel", kEmuSerial}, {"range_deliver_kernel", kEmuSerial},
+                                   {nullptr, kEmuNone}};
 
 int main(int argc, char** argv) {
     if (argc > 1 && !strcmp(argv[1], "range")) return range_main();
@@ -569,10 +406,5 @@ int main(int argc, char** argv) {
             unpack_case("unpack residues", es, pa);
         }
     unpack_case("unpack, no entry", {}, 0);
-    if (g_failures) {
-        fprintf(stderr, "emu_pack: %d failures\n", g_failures);
-        return 1;
-    }
-    printf("emu_pack ok\n");
-    return 0;
+    return emu_finish("emu_pack");
 }

@@ -1,147 +1,29 @@
 // Lane emulator of the zero-copy scatter-gather kernels (debug/test tooling,
 // tools/emu): compiles the unmodified csrc/lz4e_sg.hip as host C++ and runs
-// sg_gather_kernel and sg_deliver_kernel with every lane's work done by a
-// host thread, under the same emulated <hip/hip_runtime.h> as the other two
-// kernel files.  Stand-alone (its own main): built by EMU_SG=1 build.sh, run
+// sg_gather_kernel and sg_deliver_kernel lane by lane, under the same
+// emulated <hip/hip_runtime.h> as the other kernel files.  Stand-alone (its own main): built by EMU_SG=1 build.sh, run
 // by tests/test_emulator_sg.py under ASan + UBSan.
 //
 // The kernels work on the CALLER's memory and must not touch a byte outside
 // [src, src + n) or [dst, dst + n).  So every source segment and every
 // destination here is its own heap allocation that ends exactly at the
 // buffer's last byte (ASan's redzone follows it: one byte of over-read or
-// over-write is a report).  ASan hands out 16-B aligned blocks, so a buffer at
-// alignment a sits a bytes into its block: the whole 8-byte granules of that
-// prefix are poisoned, the up to 7 bytes left (ASan cannot poison the front
-// of a granule) hold a canary that is checked after the run.
+// over-write is a report), at a chosen alignment mod 16 with a poisoned
+// prefix and a canary that is checked after the run (emu_harness.h, Buf).
 //
 // The two kernels have no barrier and no cross-lane operation, so a
-// workgroup's 256 lanes are run by 8 host threads, 32 lanes each, one
-// workgroup after the other.
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <thread>
-#include <vector>
-
-#include <hip/hip_runtime.h>
+// workgroup's lanes run one after the other on the calling thread (the
+// harness, its Buf and its kernel modes: emu_harness.h).
+#include "emu_harness.h"
 
 #include "lz4e_sg.hip"
 
 #include "lz4e.h"
 
-#if defined(__has_feature)
-#if __has_feature(address_sanitizer)
-#include <sanitizer/asan_interface.h>
-#define EMU_POISON(p, n) __asan_poison_memory_region((p), (n))
-#define EMU_UNPOISON(p, n) __asan_unpoison_memory_region((p), (n))
-#endif
-#endif
-#ifndef EMU_POISON
-#define EMU_POISON(p, n) ((void)0)
-#define EMU_UNPOISON(p, n) ((void)0)
-#endif
-
-thread_local EmuWave* g_emu_wave;
-thread_local uint32_t g_emu_lane;
-thread_local EmuBarrier* g_emu_group;
-dim3 blockIdx, gridDim;
-thread_local dim3 threadIdx;
-
-// A pool of host threads that lives as long as the program (thousands of
-// small launches: a fresh set of threads for each was most of the run time).
-namespace {
-constexpr uint32_t kHostThreads = 8;
-struct LanePool {
-    EmuBarrier start{kHostThreads + 1}, end{kHostThreads + 1};
-    std::function<void()>* body = nullptr;
-    uint32_t threads = 0;
-    bool quit = false;
-    std::vector<std::thread> th;
-    LanePool() {
-        for (uint32_t w = 0; w < kHostThreads; ++w)
-            th.emplace_back([this, w]() {
-                for (;;) {
-                    start.arrive_and_wait();
-                    if (quit) return;
-                    for (uint32_t t = w; t < threads; t += kHostThreads) {
-                        g_emu_lane = t % 64;
-                        threadIdx = dim3(t);
-                        (*body)();
-                    }
-                    end.arrive_and_wait();
-                }
-            });
-    }
-    ~LanePool() {
-        quit = true;
-        start.arrive_and_wait();
-        for (auto& x : th) x.join();
-    }
-};
-}  // namespace
-
-void emu_launch(uint32_t nblocks, uint32_t threads, std::function<void()> body) {
-    static LanePool pool;
-    gridDim = dim3(nblocks);
-    pool.body = &body;
-    pool.threads = threads;
-    for (uint32_t b = 0; b < nblocks; ++b) {
-        blockIdx = dim3(b);
-        pool.start.arrive_and_wait();
-        pool.end.arrive_and_wait();
-    }
-}
-
-namespace {
-
-int g_failures = 0;
-#define CHECK(c, ...)                        \
-    do {                                     \
-        if (!(c)) {                          \
-            fprintf(stderr, "FAIL: " __VA_ARGS__); \
-            fprintf(stderr, "\n");           \
-            g_failures++;                    \
-        }                                    \
-    } while (0)
-
 uint32_t g_rng = 12345;
-uint8_t rnd() {
-    g_rng = g_rng * 1664525u + 1013904223u;
-    return (uint8_t)(g_rng >> 24);
-}
+uint8_t rnd() { return (uint8_t)(emu_lcg(g_rng) >> 24); }
 
-constexpr uint8_t kCanary = 0xC3;
-
-// n bytes at alignment `align` (mod 16), ending where their heap block ends.
-struct Buf {
-    uint8_t* base;
-    uint8_t* p;
-    size_t align, n;
-    Buf(size_t align_, size_t n_) : align(align_ & 15), n(n_) {
-        base = static_cast<uint8_t*>(malloc(align + n));
-        if (!base) abort();
-        p = base + align;
-        memset(base, kCanary, align);
-        EMU_POISON(base, align & ~size_t(7));
-    }
-    Buf(const Buf&) = delete;
-    Buf& operator=(const Buf&) = delete;
-    ~Buf() {
-        EMU_UNPOISON(base, align & ~size_t(7));
-        free(base);
-    }
-    void fill_random() {
-        for (size_t i = 0; i < n; ++i) p[i] = rnd();
-    }
-    void fill(uint8_t v) { memset(p, v, n); }
-    bool canary_ok() const {
-        for (size_t i = align & ~size_t(7); i < align; ++i)
-            if (base[i] != kCanary) return false;
-        return true;
-    }
-};
+namespace {
 
 // The host gather the staged path uses (csrc/lz4e_host.hip, sg_gather), restated.
 void sg_gather_ref(const struct bio_vec* bv, const struct bvec_iter& it, uint8_t* to, uint32_t len) {
@@ -259,6 +141,8 @@ void deliver_case(const DeliverCase& c) {
 
 }  // namespace
 
+const EmuKernelMode emu_modes[] = {{"sg_gather_kernel", kEmuSerial}, {"sg_deliver_kernel", kEmuSerial}, {nullptr, kEmuNone}};
+
 int main() {
     const uint32_t small[] = {1, 15, 16, 17, 31, 33}, large[] = {511, 512, 4096, 4097};
     // ---- gather ----
@@ -312,10 +196,5 @@ int main() {
             deliver_case({len, ret, il, true, 0, k, fa, da, true});          // frame_cap == 0
         }
     deliver_case({0, 1, 0, true, 1, 0, 3, 7, false});  // an empty request: a 1-byte frame, no data
-    if (g_failures) {
-        fprintf(stderr, "emu_sg: %d failures\n", g_failures);
-        return 1;
-    }
-    printf("emu_sg ok\n");
-    return 0;
+    return emu_finish("emu_sg");
 }

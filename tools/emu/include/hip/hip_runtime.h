@@ -125,10 +125,11 @@ inline uint64_t emu_gather(uint64_t v, uint32_t from) {
 }
 inline void __syncthreads() { g_emu_group->arrive_and_wait(); }
 
-// Runs grid blocks one after the other, each as `threads` host threads.
-void emu_launch(uint32_t nblocks, uint32_t threads, std::function<void()> body);
+// Runs grid blocks one after the other, each in the mode the program's table
+// gives the kernel's name (tools/emu/emu_harness.h).
+void emu_launch(const char* kernel, uint32_t nblocks, uint32_t threads, std::function<void()> body);
 #define hipLaunchKernelGGL(k, grid, block, lds, stream, ...) \
-    emu_launch((grid).x, (block).x, [&]() { k(__VA_ARGS__); })
+    emu_launch(#k, (grid).x, (block).x, [&]() { k(__VA_ARGS__); })
 
 // ---- amdgcn builtins (csrc/lz4e_wave.h) ------------------------------------
 inline uint32_t __builtin_amdgcn_mbcnt_lo(uint32_t mask, uint32_t base) {
