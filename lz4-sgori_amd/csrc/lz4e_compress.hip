@@ -58,6 +58,14 @@ namespace lz4e {
 namespace {
 
 constexpr uint32_t kTableBytes = 16384;  // 1 << LZ4E_MEMORY_USAGE
+// A workgroup's LDS behind the table.  The LDS-image kernel: the staged block
+// (16 KiB + 4 KiB: eight workgroups fill a CU's 160 KiB exactly, so it has no
+// room for more).  The HBM-image kernel: the two-wave hand-over (FlushLds,
+// 32 bytes), then the parser's 64 clash-group slots (group_lanes).
+constexpr uint32_t kStageOff = kTableBytes;
+constexpr uint32_t kFlushLdsOff = kTableBytes;
+constexpr uint32_t kGroupLdsOff = kFlushLdsOff + 32;
+constexpr uint32_t kGroupLdsBytes = 64 * sizeof(uint64_t);
 constexpr uint32_t kStripe = 256;        // bytes covered by one stripe (lane k: X-4+4k)
 
 typedef __attribute__((address_space(1))) uint8_t gu8;
@@ -439,6 +447,7 @@ struct FlushLds {
     uint32_t a0, a1, pad[2];
 };
 constexpr uint32_t kFlushLdsBytes = sizeof(FlushLds);
+static_assert(kFlushLdsOff + kFlushLdsBytes == kGroupLdsOff, "the slots follow the hand-over");
 constexpr uint32_t kPubBatch = kWave;
 #ifndef LZ4E_CSPIN_MAX
 #define LZ4E_CSPIN_MAX (1u << 23)
@@ -573,6 +582,24 @@ LZ4E_DEV void chain_out(gu8* out, uint32_t& op, gu64* rec, uint32_t& nrec, uint3
     }
 }
 
+// The lanes of my clash group, by an exchange through the wave's 64 LDS slots
+// (slot i belongs to window lane i).  key < 64 names the group of a valid
+// lane: the lane of its winning put, which is valid and has key == lane.  The
+// winners clear their slots, every valid lane ORs its bit into its group's
+// slot and reads the slot back: three LDS operations where one ballot per key
+// bit and the mask algebra around it took about 60 VALU.  A lane alone in its
+// group reads exactly its own bit.  An invalid lane passes its own number as
+// key: no valid lane names it, so it is such a group of one, and only the
+// winners' store needs a lane mask.
+LZ4E_DEV uint64_t group_lanes(uint64_t* slot, uint32_t key, uint32_t lane) {
+    uint64_t* const mine = slot + (key & (kWave - 1));  // (inside the 64 slots whatever the key)
+    if (key == lane) slot[lane] = 0;
+    lockstep();
+    __hip_atomic_fetch_or(mine, 1ull << lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    lockstep();
+    return *mine;
+}
+
 constexpr uint32_t kFwdW = 8;            // dwords of forward bytes held per position
 constexpr uint32_t kFwd = 4 * kFwdW;      // 32 bytes: matches shorter than this stay in registers
 constexpr uint32_t kLong = 1u << 31;  // ml flag: kFwd bytes equal, the count goes on
@@ -698,7 +725,8 @@ LZ4E_DEV CResult compress_block(const IMG& img, uint32_t* smem, uint32_t n, gu8*
     static_assert(kDefer || !kTwo, "the flusher wave emits records");
     CResult res;
     const uint32_t rmask = kTwo ? rlim + (kWave - 1) : ~0u;
-    [[maybe_unused]] FlushLds* const S = reinterpret_cast<FlushLds*>(smem + kTableBytes / 4);
+    [[maybe_unused]] FlushLds* const S = reinterpret_cast<FlushLds*>(smem + kFlushLdsOff / 4);
+    [[maybe_unused]] uint64_t* const X = reinterpret_cast<uint64_t*>(smem + kGroupLdsOff / 4);  // clash-group slots
     [[maybe_unused]] uint32_t pubd = 0, cons = 0;  // kTwo: records published, records consumed (a copy)
     // Dictionary mode (D > 0): the image is [D dictionary bytes | the n-byte
     // block], the parse starts at D and the table was preloaded from the
@@ -841,8 +869,10 @@ LZ4E_DEV CResult compress_block(const IMG& img, uint32_t* smem, uint32_t n, gu8*
                 // A valid lane reads back the position of its group's winning
                 // put, so rb - B names the group (invalid lanes: none; their
                 // `same` only steers the walk between two exact table builds).
-                const uint64_t vmask = ballot(valid);
-                const uint64_t m = match_any6(rb - B) & vmask;
+                // (the LDS-image kernel has no LDS left for the slots: ballots)
+                uint64_t m;
+                if constexpr (IMG::kInLds) m = match_any6(rb - B) & ballot(valid);
+                else m = group_lanes(X, rb - B, lane);
                 if (valid && (m & (m - 1))) same = m;
             }
             const uint64_t clash = ballot(same != 0);
@@ -995,29 +1025,44 @@ LZ4E_DEV CResult compress_block(const IMG& img, uint32_t* smem, uint32_t n, gu8*
                             // put) let one step read four links with independent
                             // readlanes instead of one dependent readlane each.
                             // (every lane takes part in each shuffle)
+                            // The walk ends after a link whose target is past
+                            // the window (>= 64) or whose own link is kStop:
+                            // kEnd, the spare bit above kStop, says so for
+                            // every lane and each of the four links at once,
+                            // and the scalar loop tests that one bit per link.
+                            constexpr uint32_t kEnd = kStop << 1;
+                            // j | kEnd iff j >= 64 or nxt (the link after j) is kStop; j, nxt < 256
+                            auto flagged = [](uint32_t j, uint32_t nxt) {
+                                return j | (((j | (nxt & kStop)) + 0xC0) & kEnd);
+                            };
                             const uint32_t g1 = shfl(fc, fc & 63);
                             const uint32_t J2 = fc < 64 ? g1 : fc;
                             const uint32_t g2 = shfl(fc, J2 & 63), g3 = shfl(J2, J2 & 63);
                             const uint32_t J3 = J2 < 64 ? g2 : J2;
                             const uint32_t J4 = J2 < 64 ? g3 : J2;
+                            const uint32_t g4 = shfl(fc, J4 & 63);
+                            const uint32_t F1 = flagged(fc, g1), F2 = flagged(J2, g2);
+                            const uint32_t F3 = flagged(J3, J4), F4 = flagged(J4, g4);
                             k = ks;
                             evm = 0;
-                            while (k < 64) {
-                                const uint32_t x1 = lane_val(fc, k), x2 = lane_val(J2, k);
-                                const uint32_t x3 = lane_val(J3, k), x4 = lane_val(J4, k);
-                                if (x1 & kStop) break;
-                                evm |= 1ull << k;
-                                if (x1 >= 64) { k = x1; break; }
-                                if (x2 & kStop) { k = x1; break; }
-                                evm |= 1ull << x1;
-                                if (x2 >= 64) { k = x2; break; }
-                                if (x3 & kStop) { k = x2; break; }
-                                evm |= 1ull << x2;
-                                if (x3 >= 64) { k = x3; break; }
-                                if (x4 & kStop) { k = x3; break; }
-                                evm |= 1ull << x3;
-                                k = x4;
-                            }
+                            if (!(lane_val(fc, ks) & kStop))
+                                for (;;) {  // here k < 64 and fc[k] is a link: k is an event
+                                    const uint32_t x1 = lane_val(F1, k), x2 = lane_val(F2, k);
+                                    const uint32_t x3 = lane_val(F3, k), x4 = lane_val(F4, k);
+                                    evm |= 1ull << k;
+                                    k = x1;
+                                    if (x1 & kEnd) break;
+                                    evm |= 1ull << x1;
+                                    k = x2;
+                                    if (x2 & kEnd) break;
+                                    evm |= 1ull << x2;
+                                    k = x3;
+                                    if (x3 & kEnd) break;
+                                    evm |= 1ull << x3;
+                                    k = x4;
+                                    if (x4 & kEnd) break;
+                                }
+                            k &= kStop - 1;  // (the walk never ends on kStop itself)
                             nev = popc64(evm);
                             // the chain's puts (e-2 and e of every event, the probes
                             // (l, jv(l)] of its searches), all lanes at once
@@ -1557,11 +1602,11 @@ __global__ __launch_bounds__((kTwoWave<kLdsInput, kStamps, kRecords> ? 2 : 1) * 
     }
     if constexpr (kTwo) {
         // pub, cons, done, abort
-        if (wave == 1 && lane < 4) smem[kTableBytes / 4 + lane] = 0;
+        if (wave == 1 && lane < 4) smem[kFlushLdsOff / 4 + lane] = 0;
     }
 
     if constexpr (kLdsInput) {
-        uint32_t* inw = smem + kTableBytes / 4;
+        uint32_t* inw = smem + kStageOff / 4;
         stage_block(inw, in, n, lane);
         block_sync();
         const LdsImage img{inw, n == 0 ? 0 : (n - 1) >> 2};
@@ -1586,7 +1631,7 @@ __global__ __launch_bounds__((kTwoWave<kLdsInput, kStamps, kRecords> ? 2 : 1) * 
                 // any other block emits inline on wave 0
                 const uint64_t bound = (uint64_t)n + n / 255 + 16;
                 if (records != nullptr && cap >= bound && n < (1u << kRecLenBits))
-                    flusher_wave((FlushLds*)(smem + kTableBytes / 4), img, out,
+                    flusher_wave((FlushLds*)(smem + kFlushLdsOff / 4), img, out,
                                  (const gu64*)(records + (size_t)b * nrecords), nrecords, n, D, ret, aux, b,
                                  lane);
                 return;
@@ -1826,7 +1871,7 @@ hipError_t launch_compress_impl(const CompressBatch& a, hipStream_t stream, uint
     const dim3 grid(a.nblocks), block(kWave);
     uint32_t lds = compress_lds_bytes(a.max_len, lds_input);
     constexpr bool kTwo = kTwoWave<false, kStamps, true>;
-    if (kTwo && !lds_input) lds += kFlushLdsBytes;
+    if (!lds_input) lds += kFlushLdsBytes + kGroupLdsBytes;  // (the one-wave stamped build keeps the layout)
     // heavy blocks first (see weight_kernel)
     const int om = launch_order_mode(true);
     const bool use_order = !lds_input && (om == kOrderAlways || (om == kOrderAuto && a.nblocks >= kOrderMinBlocks &&
